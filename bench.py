@@ -18,7 +18,11 @@ depend on the segment length.  Synthetic PCM is resident in HBM before the timed
 Streams are independent: rank r owns streams [64 r, 64 r + 64), there is no data-path collective
 ("scaling": "weak"); torch.distributed (RCCL) is used only for the barrier and the max-over-ranks.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5     # the headline figure alone: set-up, warm-up, the timed steps, one line
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full     # + every other leg: profiled steps / roofline, PCIe-inclusive and
+                                                      #   offline legs, sustained run, stream timeline, self-check, parity and
+                                                      #   reproducibility checks, BASELINE configs[2] / [4], CPU baselines
+    python bench.py ... --dump-outputs DIR            # the token lists the last timed step handed out, as DIR/<name>.npy
     python bench.py --gpus N ...                      # spawns N ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -468,6 +472,28 @@ def reproducibility_check(cfg, sd, B, dtype, beam, depth, device, n_chunks=24, r
         eng.close()
 
 
+def dump_outputs(path, collected, k_lo, k_hi, n_streams, rank=0, limit_bytes=60 << 20):
+    """--dump-outputs: what the LAST timed step handed to its caller.  `collected` = (chunk index of the model step, token lists of
+    all streams as lasr_fetch_many returned them) in collection order; kept are the model steps of the chunks [k_lo, k_hi).
+    tokens.npy: float32 [model steps, streams, longest list], padded with -1 (beam search: every list is the whole best hypothesis
+    so far); token_counts.npy: float32 [model steps, streams].  Token ids are far below 2^24, so float32 holds them exactly.  Should
+    the arrays exceed limit_bytes, the earliest model steps of the step are left out (the same ones in every run)."""
+    steps = [toks for k, toks in collected if k is not None and k_lo <= k < k_hi]
+    width = max([len(t) for toks in steps for t in toks] + [1])
+    keep = max(1, min(len(steps), limit_bytes // (4 * n_streams * (width + 1))))
+    steps = steps[len(steps) - keep:]
+    tokens = np.full((len(steps), n_streams, width), -1.0, dtype=np.float32)
+    counts = np.zeros((len(steps), n_streams), dtype=np.float32)
+    for i, toks in enumerate(steps):
+        for r, t in enumerate(toks):
+            tokens[i, r, :len(t)] = t
+            counts[i, r] = len(t)
+    os.makedirs(path, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(path, f"tokens{tag}.npy"), tokens)
+    np.save(os.path.join(path, f"token_counts{tag}.npy"), counts)
+
+
 def other_config_legs():
     """The BASELINE configs the headline line does not run (bf16 + beam search), each as a CHILD run of this script on the same GPU
     behind the headline's own legs (the parent is idle meanwhile): same measurement code, same line; the fields a reader needs are
@@ -475,7 +501,7 @@ def other_config_legs():
     legs = []
     for tag, argv in OTHER_CONFIGS:
         t0 = time.perf_counter()
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1"] + argv + ["--no-cpu-baseline", "--no-extras", "--sustained-s", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1"] + argv + ["--full", "--no-cpu-baseline", "--no-extras", "--sustained-s", "0",
                                                                                   "--other-configs", "0", "--emu-parity", "4:24"]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
         try:
@@ -513,6 +539,15 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 = BASELINE configs[1] (the headline metric); bf16 = configs[2] arithmetic "
                          "(bf16 MFMA operands, f32 accumulate/state)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the profiled steps behind the timed region (roofline), the "
+                         "isolated cell micro-benchmark, the stream-overlap probe, the PCIe-inclusive and offline legs, the sustained "
+                         "run, the stream timeline, the self-check, --emu-parity, the reproducibility check, the other BASELINE "
+                         "configs and the CPU baselines (each with its own switch below).  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step handed to its caller -- the token lists of every "
+                         "stream for each of its model steps -- as DIR/tokens.npy and DIR/token_counts.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the offline and PCIe-inclusive legs")
     ap.add_argument("--host-pcm", action="store_true",
@@ -565,6 +600,10 @@ def main():
                     help="CPU-only: exercise sharding + aggregation over gloo (no GPU work)")
     args = ap.parse_args()
 
+    if not args.full:
+        # a plain run measures the headline figure and nothing else: every leg that takes a run, a replay or a region of its own is off
+        args.no_cpu_baseline = args.no_extras = True
+        args.sustained_s, args.other_configs, args.check_rows, args.prof_steps, args.emu_parity = 0.0, 0, 0, 0, None
     if args.depth is None:
         # Steps in flight trade latency for throughput: a deeper pipeline lets bursty rows fall behind while the others run ahead,
         # so a decode iteration (which streams the same weights for 3 rows as for 64) serves more rows -- greedy, f32 / bf16 (round 5,
@@ -636,7 +675,7 @@ def main():
     pcm_host = np.stack([synth.synth_pcm(1, n_chunks * CHUNK, seed=1234 + s)[0] for s in my_streams])
     pcm_dev = torch.as_tensor(pcm_host.reshape(B, n_chunks, CHUNK).transpose(1, 0, 2).copy()).to(device)
     pcm_host_chunks = np.ascontiguousarray(pcm_host.reshape(B, n_chunks, CHUNK).transpose(1, 0, 2))
-    pcm_pinned_chunks = torch.from_numpy(pcm_host_chunks).pin_memory()      # PCIe-inclusive legs: pinned client buffers
+    pcm_pinned_chunks = torch.from_numpy(pcm_host_chunks).pin_memory() if extras else None      # PCIe-inclusive legs: pinned client buffers
     slots = [eng.open() for _ in range(B)]
     assert slots == list(range(B))
 
@@ -649,7 +688,11 @@ def main():
     recording = [True]
     host_us = {"push": 0.0, "submit": 0.0, "wait": 0.0, "fetch": 0.0, "n_model_steps": 0}   # host time per call kind (timed region)
 
-    def record(tok_lists):
+    dumped = [] if args.dump_outputs else None    # --dump-outputs: (chunk index of the model step, token lists as fetched)
+
+    def record(tok_lists, k=None):
+        if dumped is not None:
+            dumped.append((k, tok_lists))
         if recording[0]:
             for r in range(NCHK):
                 rec_steps[r].append(tok_lists[r])
@@ -682,7 +725,7 @@ def main():
         if not pipelined:
             if eng.step(slots):
                 toks = eng.fetch_many(slots, cap=FETCH_CAP)
-                record(toks)
+                record(toks, k)
                 ntok = sum(len(t) for t in toks)
                 done = 1
                 if lat_out is not None:
@@ -707,9 +750,9 @@ def main():
         toks = eng.fetch_many(slots, cap=FETCH_CAP)
         host_us["wait"] += t1 - t0
         host_us["fetch"] += time.perf_counter() - t1
-        record(toks)
-        ntok = sum(len(t) for t in toks)
         kk = order.pop(0)
+        record(toks, kk)
+        ntok = sum(len(t) for t in toks)
         if lat_out is not None:
             lat_out.append(time.perf_counter() - push_t.pop(kk))
         return 1, ntok
@@ -779,7 +822,7 @@ def main():
         host_us[k] = 0.0 if k != "n_model_steps" else 0
     if dist is not None:
         host_barrier(dist)                        # (creates the gloo group outside the timed region)
-    overlap_before = eng.overlap_probe(10000) if pipelined else float("nan")      # 2 x 10 ms: do the engine's streams overlap?
+    overlap_before = eng.overlap_probe(10000) if pipelined and args.full else float("nan")      # 2 x 10 ms: do the engine's streams overlap?
     nb, nb_start = None, None
     if args.neighbour:
         kind, wgs, ms = args.neighbour.split(":")
@@ -794,6 +837,9 @@ def main():
         nb["unit"] = "TFLOP/s (f32 MFMA)" if nb["kind"] == "mfma" else "GB/s"
     host_timed = dict(host_us)
     recording[0] = False                          # the self-check compares everything up to the end of the timed region
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, P + W + K - CPS, P + W + K, B, rank)
+        dumped = None
     if args.trace:
         with open(args.trace, "w") as f:
             json.dump({"marks": eng.trace_read(), "elapsed_us": 1e6 * elapsed, "chunks": K}, f)
@@ -826,7 +872,7 @@ def main():
     elapsed_max, audio_total = aggregate(dist, elapsed, audio_local, device)
     # per-rank figures on rank 0 (a straggler is visible in the driver's N-GPU line): value, elapsed, host time per model step
     nms = max(1, host_timed["n_model_steps"])
-    overlap_after = eng.overlap_probe(10000) if pipelined else float("nan")       # ... and after the job's RCCL collectives
+    overlap_after = eng.overlap_probe(10000) if pipelined and args.full else float("nan")       # ... and after the job's RCCL collectives
     mine = [float(rank), audio_local / elapsed, elapsed, 1e6 * host_timed["push"] / nms, 1e6 * host_timed["submit"] / nms,
             1e6 * host_timed["wait"] / nms, 1e6 * host_timed["fetch"] / nms, overlap_before, overlap_after, cpu_timed / max(1e-9, elapsed),
             float(-1 if numa_node is None else numa_node), float(numa_cpus), float(eng_cfg.get("pump_nap_pct", 0)),
@@ -910,7 +956,7 @@ def main():
                           "host_us_per_model_step": {"push": round(v[3], 1), "submit": round(v[4], 1), "wait_incl_spin": round(v[5], 1),
                                                      "fetch": round(v[6], 1), "busy": round(v[3] + v[4] + v[6], 1)},
                           # two 10 ms delay kernels, one per engine stream, wall time / 10 ms: ~1 = concurrent, ~2 = one hardware queue
-                          "overlap_probe": {"before_timed": round(v[7], 3), "after_collectives": round(v[8], 3)},
+                          "overlap_probe": ({"before_timed": round(v[7], 3), "after_collectives": round(v[8], 3)} if v[7] == v[7] else None),
                           "streams_overlap": bool(v[7] < 1.5) if v[7] == v[7] else None,
                           # CPU seconds of the whole process (API thread + the library's pump and push-helper threads) per second of
                           # the timed region: how many host cores this rank keeps busy (spinning included)
@@ -962,7 +1008,11 @@ def main():
                                        "frac": round(job_tflops / (PEAK_BF16_MFMA_TFLOPS if bf else PEAK_F32_MFMA_TFLOPS), 4),
                                        "note": "algorithmic FLOP of SURVEY 8d per frame (measured tokens/frame) x frames/s / MFMA peak"}},
         }
-        if bf:
+        if not args.full:
+            # the per-kernel figures come from profiled steps and a micro-benchmark behind the timed region: --full
+            out["roofline"] = {"whole_job": out["roofline"]["whole_job"],
+                               "note": "per-kernel figures (launch_us, frac, launch_us_isolated) take steps of their own: --full"}
+        elif bf:
             # 64 rows x 2 flop / 2 B = 64 flop/B is far below the bf16 ridge (2500 TFLOP/s / 8 TB/s = 312):
             # the bf16 cell is bound by streaming its weights, so it is priced against HBM bandwidth
             gbs = wbytes_mean / (dur_us * 1e-6) / 1e9
@@ -970,10 +1020,11 @@ def main():
                                     "frac": round(gbs / PEAK_HBM_GBS, 4),
                                     "frac_rocprof": round(wbytes_mean / (rocprof_us * 1e-6) / 1e9 / PEAK_HBM_GBS, 4) if rocprof_us else None,
                                     "note": "algorithmic bytes = packed bf16 weights of one cell (W_ih + W_hh)"})
-        try:                                                               # the kernel alone on the GPU (micro-benchmark)
-            out["roofline"]["launch_us_isolated"] = round(eng.bench_cell(layer=1, iters=300), 3)
-        except Exception as e:
-            out["roofline"]["launch_us_isolated"] = None
+        if args.full:
+            try:                                                           # the kernel alone on the GPU (micro-benchmark)
+                out["roofline"]["launch_us_isolated"] = round(eng.bench_cell(layer=1, iters=300), 3)
+            except Exception as e:
+                out["roofline"]["launch_us_isolated"] = None
         if extras:
             # PCIe-inclusive leg (SURVEY 8d "from first PCM byte available on host"): the same K steps again with every
             # chunk handed to lasr_push_pcm as a host array; reported beside the headline, never as `value`

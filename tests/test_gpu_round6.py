@@ -186,7 +186,8 @@ def test_native_front_reset_rule_judges_text(reset_steps, depth):
 
 # ------------------------------------------------------------------------------- real speech (configs[0]'s utterance)
 def speech(golden_dir):
-    g = np.load(os.path.join(golden_dir, "speech_demo.npz"))
+    g = dict(np.load(os.path.join(golden_dir, "speech_demo.npz")))
+    g.update(np.load(os.path.join(golden_dir, "speech_demo_logmel.npz")))      # (the log-mel in a file of its own: each stays under 1 MiB)
     return g, (g["pcm_i16"].astype(np.float32) / 32768.0)
 
 

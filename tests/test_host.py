@@ -15,11 +15,11 @@ from libreasr_amd.lib.language import IdLanguage
 from libreasr_amd.lib.utils import tensorize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_FLAC = "/root/reference/demo/3729-6852-0035.flac"
-REF_YAML = "/root/reference/config/testing.yaml"
+# the reference's demo utterance and its testing configuration, stored with the goldens (data and settings only)
+REF_FLAC = os.path.join(ROOT, "tests", "golden", "demo_3729-6852-0035.flac")
+REF_YAML = os.path.join(ROOT, "tests", "golden", "reference_testing.yaml")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FLAC), reason="reference tree not mounted (GPU box)")
 def test_flac_decoder_matches_streaminfo_md5(golden_dir):
     from libreasr_amd import flac
     pcm, sr, md5_ok = flac.decode(REF_FLAC)
@@ -35,7 +35,6 @@ def test_flac_decoder_matches_streaminfo_md5(golden_dir):
     np.testing.assert_allclose(feats[-2:], g["feats_last"], atol=3e-4)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not mounted (GPU box)")
 def test_reference_yaml_and_overrides():
     conf = cfgmod.open_config(REF_YAML)
     inf = cfgmod.apply_overrides(conf, inference=True, lang=None)
@@ -507,3 +506,17 @@ def test_abi_consumer_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == (0 if torch.cuda.is_available() else 10), (r.returncode, r.stdout, r.stderr[-2000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the model steps of the last timed step only, float32, padded with -1; a size limit drops the
+    earliest model steps, never a stream."""
+    import bench
+    collected = [(k, [[k, k + 1], [], [7]]) for k in range(0, 12, 2)] + [(None, [[9], [9], [9]])]
+    bench.dump_outputs(str(tmp_path), collected, 6, 12, 3)
+    t, c = np.load(tmp_path / "tokens.npy"), np.load(tmp_path / "token_counts.npy")
+    assert t.dtype == c.dtype == np.float32 and t.shape == (3, 3, 2) and c.shape == (3, 3)
+    assert t[0].tolist() == [[6, 7], [-1, -1], [7, -1]] and c.tolist() == [[2, 0, 1]] * 3
+    bench.dump_outputs(str(tmp_path), collected, 0, 12, 3, rank=1, limit_bytes=2 * 4 * 3 * 3)
+    t = np.load(tmp_path / "tokens_rank1.npy")
+    assert t.shape == (2, 3, 2) and t[-1, 0].tolist() == [10, 11]
