@@ -91,16 +91,15 @@ int ensure_T(lasr_ctx* c, int T) {
     RC(dalloc(c, (char**)&c->x0, (size_t)cap * M * F * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[0], (size_t)cap * M * H * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[1], (size_t)cap * M * H * c->esz));
-    RC(dalloc(c, &c->pe_sync, (size_t)cap * M * J)); HIPCHK(c, hipMemset(c->pe_sync, 0, sizeof(float) * (size_t)cap * M * J));
+    RC(dalloc0(c, &c->pe_sync, (size_t)cap * M * J));
     c->pe = c->pe_sync;
     const int mi = std::max(c->d.max_iters_offline, c->d.max_iters_stream);
     c->tok_cap_alloc = cap * mi;
     // [ntok M][tokens M x tok_cap]: one contiguous block so a group's results reach the host in one copy
-    RC(dalloc(c, &c->ds.step_ntok, (size_t)M + (size_t)M * c->tok_cap_alloc));
-    HIPCHK(c, hipMemset(c->ds.step_ntok, 0, sizeof(int) * ((size_t)M + (size_t)M * c->tok_cap_alloc)));
+    RC(dalloc0(c, &c->ds.step_ntok, (size_t)M + (size_t)M * c->tok_cap_alloc));
     c->ds.step_tok = c->ds.step_ntok + M;
     c->n_iter_slots = cap * mi + 8;
-    RC(dalloc(c, &c->ds.unfinished, (size_t)c->n_iter_slots)); HIPCHK(c, hipMemset(c->ds.unfinished, 0, sizeof(int) * (size_t)c->n_iter_slots));
+    RC(dalloc0(c, &c->ds.unfinished, (size_t)c->n_iter_slots));
     if (c->W > 1) {
         dfree(c, c->b_trellis); c->b_trellis = nullptr;
         RC(dalloc(c, &c->b_trellis, (size_t)c->n_iter_slots * c->Md));

@@ -50,18 +50,15 @@ struct lasr_ctx {
     float *b1 = nullptr, *b2 = nullptr;
 
     // recurrent state (row == slot)
-    std::vector<void*> enc_h[2], pred_h[2], pred_y;      // element-typed (A operands)
-    std::vector<float*> enc_c, pred_c;
+    std::vector<void*> enc_h[2], pred_h[2], pred_y[2];   // element-typed (A operands)
+    std::vector<float*> enc_c, pred_c[2];
     int cell_nw = 0;                // waves per encoder-cell workgroup (0: 4 for f32, 8 for bf16); LASR_CELL_NW
     bool enc_u12 = false;           // encoder cell tiling D (12 units x 64 rows per workgroup, EpiLSTMe): bf16, H % 12 == 0, M % 64 == 0,
                                     // H / 12 * M / 64 >= 256 workgroups; LASR_ENC_U12 overrides
     int dec_prio = 1, cell_prio = 0;   // s_setprio of the decode-stream GEMMs (+4 % at 6 steps in flight, round 2) / of everything else
     int logits_mt = 2;              // m-tiles per workgroup of the logits GEMM (la x 64 rows must not re-read W2 per 16-row tile)
-    // beam search: c, BN(h) and pp ping-pong like h (every slot may be re-parented each round):
-    // parity 0 = pred_c / pred_y / pp, parity 1 = the *1 buffers; all follow pred_par
-    std::vector<float*> pred_c1;
-    std::vector<void*> pred_y1;
-    float* pp1 = nullptr;
+    // beam search: c, BN(h) and pp ping-pong like h (every slot may be re-parented each round): pred_c / pred_y / pp are indexed
+    // by parity and follow pred_par (par_rd / par_wr below); index 1 exists with a beam only
     double* b_score = nullptr; int *b_alive = nullptr, *b_inB = nullptr, *b_parent = nullptr, *b_trellis = nullptr;
     // host: token history of every hypothesis slot as a shared-prefix tree per stream (a round re-parents W slots: copying W
     // token vectors per round grows with the length of the stream; a node per emitted token does not)
@@ -100,7 +97,7 @@ struct lasr_ctx {
     float* pendlog = nullptr;       // LASR_DBG_PENDLOG=1 (with LASR_DBG_ENCLOG): a copy of the pending log-mel frames per logged step
     int enclog_cap = 0, enclog_n = 0;   // encoder's inputs and state behind that step: [N][2 T + 2 L][M], see lasr_debug_enclog
     std::vector<unsigned long long> tile_masks;   // per step t: m-tiles with an active row (from the host's T_row)
-    float *pp = nullptr, *logits = nullptr;
+    float *pp[2] = {nullptr, nullptr}, *logits = nullptr;
     void* ja = nullptr;             // joint activation, fragment-major, element-typed
     DecState ds{};
     int n_iter_slots = 0;
@@ -200,13 +197,13 @@ struct lasr_ctx {
         std::vector<Cell> cells;        // tiling "A"; layer 0 input side = per-token table
         void* Wout = nullptr; float* bout = nullptr;
         float *ones = nullptr, *zeros = nullptr;       // "BatchNorm fold" of a plain LSTM: y = h
-        std::vector<void*> h[2], y;     // row-major [M][H], element-typed; h ping-pongs
-        std::vector<float*> cst;        // [H][M]
+        std::vector<void*> h[2], y[2];  // row-major [M][H], element-typed; h ping-pongs
+        std::vector<float*> cst[2];     // [H][M]
         int par = 0;
-        float *raw = nullptr, *lmz = nullptr;          // [M][V] output-layer logits / standardised log-probs
-        int* valid = nullptr;
-        // beam search (rows = hypothesis slots, Md of them): c, y, lmz and valid ping-pong like h (a slot may continue any parent)
-        std::vector<void*> y1; std::vector<float*> cst1; float* lmz1 = nullptr; int* valid1 = nullptr;
+        float *raw = nullptr, *lmz[2] = {nullptr, nullptr};   // [M][V] output-layer logits / standardised log-probs
+        int* valid[2] = {nullptr, nullptr};
+        // beam search (rows = hypothesis slots, Md of them): c, y, lmz and valid ping-pong like h (a slot may continue any parent):
+        // index 1 of y / cst / lmz / valid exists with a beam only
         // int8-served form (lasr_attach_lm_int8): integer-valued bf16 weights (row-major tiles of 16 outputs, K padded to 32),
         // per-tensor weight scales, separate biases; fp32 state (h[0][l] == h[1][l] row-major [M][H], cst[l] as [H][M])
         bool q8 = false;
@@ -333,6 +330,12 @@ struct lasr_ctx {
     lasr_step_stats stats{};
 };
 
+// Ping-pong rule of everything indexed by a parity except h (pred_y / pred_c / pp under pred_par; the LM's y / cst / lmz / valid
+// under lm.par): with a beam a pass reads parity p and writes parity p ^ 1; without, they live in index 0 for both (h ping-pongs
+// either way: read [p], write [p ^ 1]).
+inline int par_rd(bool beam, int p) { return beam ? p : 0; }
+inline int par_wr(bool beam, int p) { return beam ? p ^ 1 : 0; }
+
 namespace {
 
 // c->err belongs to the API thread (lasr_last_error hands out its c_str()); the pump thread points this at its own buffer
@@ -387,6 +390,12 @@ struct RoctxRange {
     RoctxRange& operator=(const RoctxRange&) = delete;
 };
 
+#define RC(x)                \
+    do {                     \
+        int rc_ = (x);       \
+        if (rc_) return rc_; \
+    } while (0)
+
 template <class T>
 int dalloc(lasr_ctx* c, T** p, size_t n) {
     void* q = nullptr;
@@ -399,6 +408,12 @@ int dalloc(lasr_ctx* c, T** p, size_t n) {
     // previous owner of the memory left: a kernel that reads a buffer it should first have written shows up at once
     static const int poison = getenv("LASR_POISON") ? atoi(getenv("LASR_POISON")) : 0;
     if (poison && hipMemset(q, 0xff, n * sizeof(T)) != hipSuccess) return fail(c, LASR_EHIP, "poison fill failed");
+    return LASR_OK;
+}
+template <class T>
+int dalloc0(lasr_ctx* c, T** p, size_t n) {      // dalloc + zero fill (after the poison fill, if any)
+    RC(dalloc(c, p, n));
+    HIPCHK(c, hipMemset(*p, 0, n * sizeof(T)));
     return LASR_OK;
 }
 void dfree(lasr_ctx* c, void* p) {
@@ -414,11 +429,6 @@ int upload(lasr_ctx* c, T** p, const T* src, size_t n) {
     HIPCHK(c, hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice));
     return LASR_OK;
 }
-#define RC(x)                \
-    do {                     \
-        int rc_ = (x);       \
-        if (rc_) return rc_; \
-    } while (0)
 
 unsigned short host_bf16(float x) {            // round to nearest even (same as the device f32_to_bf16)
     unsigned u;

@@ -19,14 +19,14 @@ int apply_reset(lasr_ctx* c, bool any_pred, int mask = 3, bool plain_rows = fals
     }
     for (int l = 0; l < a.Lp; ++l) {
         a.pred_h[l] = c->pred_h[c->pred_par][l];
-        a.pred_c[l] = c->d.pred_cell ? ((beam && c->pred_par) ? c->pred_c1[l] : c->pred_c[l]) : nullptr;
+        a.pred_c[l] = c->d.pred_cell ? c->pred_c[par_rd(beam, c->pred_par)][l] : nullptr;
         a.pred_h0[l] = c->pred[l].h0; a.pred_c0[l] = c->pred[l].c0;
     }
     a.token = c->ds.token; a.emit = c->ds.emit;
     const bool use_bos = c->bos_ready && !beam && !plain_rows && c->W == 1 && (mask & 2);
     if (use_bos) {
         for (int l = 0; l < a.Lp; ++l) { a.bos_h[l] = c->bos_h[l]; a.bos_c[l] = c->d.pred_cell ? c->bos_c[l] : nullptr; }
-        a.bos_pp = c->bos_pp; a.pp = c->pp; a.J = c->d.joint;
+        a.bos_pp = c->bos_pp; a.pp = c->pp[0]; a.J = c->d.joint;
         any_pred = false;                    // the state after the BOS step is stored, not computed
     }
     hipLaunchKernelGGL(k_reset_rows, dim3(grid1((size_t)c->M * c->d.hidden)), dim3(256), 0, c->stream, a);
@@ -35,8 +35,9 @@ int apply_reset(lasr_ctx* c, bool any_pred, int mask = 3, bool plain_rows = fals
         const bool lb = c->W > 1 && !plain_rows;         // beam: W slots per stream, current parity of every ping-pong buffer
         la.what = c->dc.what; la.M = c->M; la.H = c->lm.H; la.L = c->lm.L; la.bf = c->lm.q8 ? 0 : c->bf;
         la.W = lb ? c->W : 1; la.Md = lb ? c->Md : c->M;
-        la.lm_valid = (lb && c->lm.par) ? c->lm.valid1 : c->lm.valid;
-        for (int l = 0; l < c->lm.L; ++l) { la.h[l] = c->lm.h[c->lm.par][l]; la.c[l] = (lb && c->lm.par) ? c->lm.cst1[l] : c->lm.cst[l]; }
+        const int lp = par_rd(lb, c->lm.par);
+        la.lm_valid = c->lm.valid[lp];
+        for (int l = 0; l < c->lm.L; ++l) { la.h[l] = c->lm.h[c->lm.par][l]; la.c[l] = c->lm.cst[lp][l]; }
         if (c->lm.q8) { la.Kp = c->lm.Kp_h; for (int l = 0; l < c->lm.L; ++l) { la.qh[l] = c->lm.qh[l]; la.sxh[l] = c->lm.sxh[l]; } }
         hipLaunchKernelGGL(k_lm_reset, dim3(grid1((size_t)c->M * c->lm.H)), dim3(256), 0, c->stream, la);
     }
@@ -178,7 +179,7 @@ void run_encoder(lasr_ctx* c, int T_max) {
     // encoder half of the joint for all frames: pe[t][r] = W1e * enc[t][r]
     const int H = c->d.hidden, J = c->d.joint;
     GemmArgs g{};
-    g.A[0] = c->ybuf[(L - 1) & 1]; g.a_mt_total[0] = mt_total; g.a_mt_off[0] = 0; g.W[0] = c->W1e;
+    set_operand(g, 0, c->ybuf[(L - 1) & 1], mt_total, 0, 0, c->W1e);
     EpiLinear::Args ea{};
     ea.bias = nullptr; ea.out = c->pe; ea.ldo = J; ea.n_rows = T_max * c->M; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
     if (c->pe == c->pe_ring) { ea.ring_base = c->fe_fused ? c->c_enc_base : c->c_enc_frames; ea.ring = lasr_ctx::RING; }   // continuous mode: per-row frame ring
@@ -248,7 +249,7 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
         if (first == 0) {
             hipLaunchKernelGGL(k_step_begin, dim3(grid1(std::max(M, c->n_iter_slots))), dim3(256), 0, c->stream, s, M,
                                c->n_iter_slots, offline ? 1 : 0);
-            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, c->stream, c->pe, c->pp, c->dec_t_idx,
+            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, c->stream, c->pe, c->pp[0], c->dec_t_idx,
                                c->T_row_dec, c->ja, J, M, c->MTj, c->pe_ring_R, c->bf, 1, M, c->la);
         }
         for (int q = 0; q < n; ++q) {

@@ -5,8 +5,12 @@
 #include <sys/prctl.h>
 #include <time.h>
 
-static void cont_poll(lasr_ctx* c);       // (pipelined protocol, below; require_idle consumes a group that was still running)
-static int flush_lazy(lasr_ctx* c);       // (deferred ring append of lasr_push_submit, below)
+// defined further down, used before
+static void cont_poll(lasr_ctx* c);       // (pipelined protocol; require_idle consumes a group that was still running)
+static int cont_pump(lasr_ctx* c, int G);
+static int pump_start(lasr_ctx* c);
+static void pump_kick(lasr_ctx* c);
+static int flush_lazy(lasr_ctx* c);       // (deferred ring append of lasr_push_submit)
 #include "lasr_cmd.hip.h"
 #include "lasr_decode.hip.h"
 #include "lasr_weights.hip.h"
@@ -158,13 +162,11 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         // flight, 92 % busy -- 8 waves win: 53.5-53.6 -> 54.2-54.6 k timed, 57.3-57.5 -> 57.6-58.3 k sustained, same box, 4 runs each:
         // profiles/r06/r06_experiments.txt T)
         if (getenv("LASR_DBG_TIMING")) {
-            RC(dalloc(c, &c->dbg, (size_t)5 * 4096 * 16));
-            HIPCHK(c, hipMemset(c->dbg, 0, sizeof(unsigned long long) * 5 * 4096 * 16));
+            RC(dalloc0(c, &c->dbg, (size_t)5 * 4096 * 16));
         }
         if (getenv("LASR_DBG_ENCLOG") && atoi(getenv("LASR_DBG_ENCLOG")) > 0) {
             c->enclog_cap = atoi(getenv("LASR_DBG_ENCLOG"));
-            RC(dalloc(c, &c->enclog, (size_t)c->enclog_cap * 32 * c->M));
-            HIPCHK(c, hipMemset(c->enclog, 0, sizeof(unsigned) * (size_t)c->enclog_cap * 32 * c->M));
+            RC(dalloc0(c, &c->enclog, (size_t)c->enclog_cap * 32 * c->M));
             if (getenv("LASR_DBG_PENDLOG") && atoi(getenv("LASR_DBG_PENDLOG")) > 0)
                 RC(dalloc(c, &c->pendlog, (size_t)c->enclog_cap * c->M * d.n_buffer * d.n_stack * d.n_mels));
         }
@@ -263,27 +265,25 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
 
     // ---- state + work buffers
     for (int p = 0; p < 2; ++p) { c->enc_h[p].resize(d.enc_layers); c->pred_h[p].resize(d.pred_layers); }
-    c->enc_c.resize(d.enc_layers); c->pred_c.assign(d.pred_layers, nullptr); c->pred_y.resize(d.pred_layers);
+    c->enc_c.resize(d.enc_layers); c->pred_c[0].assign(d.pred_layers, nullptr); c->pred_y[0].resize(d.pred_layers);
     for (int l = 0; l < d.enc_layers; ++l) {
-        for (int p = 0; p < 2; ++p) { RC(dalloc(c, (char**)&c->enc_h[p][l], (size_t)M * H * c->esz)); HIPCHK(c, hipMemset(c->enc_h[p][l], 0, (size_t)M * H * c->esz)); }
-        RC(dalloc(c, &c->enc_c[l], (size_t)M * H)); HIPCHK(c, hipMemset(c->enc_c[l], 0, (size_t)M * H * 4));
+        for (int p = 0; p < 2; ++p) { RC(dalloc0(c, (char**)&c->enc_h[p][l], (size_t)M * H * c->esz)); }
+        RC(dalloc0(c, &c->enc_c[l], (size_t)M * H));
     }
     for (int l = 0; l < d.pred_layers; ++l) {
-        for (int p = 0; p < 2; ++p) { RC(dalloc(c, (char**)&c->pred_h[p][l], (size_t)Md * H * c->esz)); HIPCHK(c, hipMemset(c->pred_h[p][l], 0, (size_t)Md * H * c->esz)); }
-        if (d.pred_cell) { RC(dalloc(c, &c->pred_c[l], (size_t)Md * H)); HIPCHK(c, hipMemset(c->pred_c[l], 0, (size_t)Md * H * 4)); }
-        RC(dalloc(c, (char**)&c->pred_y[l], (size_t)Md * H * c->esz)); HIPCHK(c, hipMemset(c->pred_y[l], 0, (size_t)Md * H * c->esz));
+        for (int p = 0; p < 2; ++p) { RC(dalloc0(c, (char**)&c->pred_h[p][l], (size_t)Md * H * c->esz)); }
+        if (d.pred_cell) RC(dalloc0(c, &c->pred_c[0][l], (size_t)Md * H));
+        RC(dalloc0(c, (char**)&c->pred_y[0][l], (size_t)Md * H * c->esz));
     }
-    RC(dalloc(c, &c->pp, (size_t)Md * J)); HIPCHK(c, hipMemset(c->pp, 0, (size_t)Md * J * 4));
+    RC(dalloc0(c, &c->pp[0], (size_t)Md * J));
     if (c->W > 1) {       // second parity of every per-hypothesis buffer + the beam bookkeeping
-        c->pred_c1.assign(d.pred_layers, nullptr); c->pred_y1.assign(d.pred_layers, nullptr);
+        c->pred_c[1].assign(d.pred_layers, nullptr); c->pred_y[1].assign(d.pred_layers, nullptr);
         for (int l = 0; l < d.pred_layers; ++l) {
-            if (d.pred_cell) { RC(dalloc(c, &c->pred_c1[l], (size_t)Md * H)); HIPCHK(c, hipMemset(c->pred_c1[l], 0, (size_t)Md * H * 4)); }
-            RC(dalloc(c, (char**)&c->pred_y1[l], (size_t)Md * H * c->esz)); HIPCHK(c, hipMemset(c->pred_y1[l], 0, (size_t)Md * H * c->esz));
+            if (d.pred_cell) RC(dalloc0(c, &c->pred_c[1][l], (size_t)Md * H));
+            RC(dalloc0(c, (char**)&c->pred_y[1][l], (size_t)Md * H * c->esz));
         }
-        RC(dalloc(c, &c->pp1, (size_t)Md * J)); HIPCHK(c, hipMemset(c->pp1, 0, (size_t)Md * J * 4));
-        RC(dalloc(c, &c->b_score, Md)); RC(dalloc(c, &c->b_alive, Md)); RC(dalloc(c, &c->b_inB, Md)); RC(dalloc(c, &c->b_parent, Md));
-        HIPCHK(c, hipMemset(c->b_score, 0, sizeof(double) * Md)); HIPCHK(c, hipMemset(c->b_alive, 0, sizeof(int) * Md));
-        HIPCHK(c, hipMemset(c->b_inB, 0, sizeof(int) * Md)); HIPCHK(c, hipMemset(c->b_parent, 0, sizeof(int) * Md));
+        RC(dalloc0(c, &c->pp[1], (size_t)Md * J));
+        RC(dalloc0(c, &c->b_score, Md)); RC(dalloc0(c, &c->b_alive, Md)); RC(dalloc0(c, &c->b_inB, Md)); RC(dalloc0(c, &c->b_parent, Md));
         c->bh.assign(M, lasr_ctx::BeamHost{});
         for (auto& b : c->bh) bh_reset(b, c->W);
         c->committed.assign(M, {}); c->committed_score.assign(M, 0.0); c->best_full.assign(M, {});
@@ -306,19 +306,15 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
             c->b_endal_host = (int*)(blk + off); c->b_endal_dev = (int*)(dblk + off);
         }
     }
-    RC(dalloc(c, (char**)&c->ja, Mj * J * c->esz)); HIPCHK(c, hipMemset(c->ja, 0, Mj * J * c->esz));
-    RC(dalloc(c, (char**)&c->cvt_a, (size_t)M * H * c->esz)); RC(dalloc(c, (char**)&c->cvt_b, (size_t)M * H * c->esz));
-    HIPCHK(c, hipMemset(c->cvt_a, 0, (size_t)M * H * c->esz)); HIPCHK(c, hipMemset(c->cvt_b, 0, (size_t)M * H * c->esz));
-    RC(dalloc(c, &c->logits, Mj * V)); HIPCHK(c, hipMemset(c->logits, 0, sizeof(float) * Mj * V));
-    RC(dalloc(c, &c->ds.t_idx, M)); RC(dalloc(c, &c->ds.iters, M)); RC(dalloc(c, &c->ds.token, Md));
-    RC(dalloc(c, &c->ds.emit, Md)); RC(dalloc(c, &c->ds.logp_sum, M));
-    RC(dalloc(c, &c->ds.sum_iters, M)); RC(dalloc(c, &c->ds.n_ones, M)); RC(dalloc(c, &c->zero_rows, M));
-    HIPCHK(c, hipMemset(c->zero_rows, 0, sizeof(int) * M));
-    RC(dalloc(c, &c->pub_arrivals, 4)); HIPCHK(c, hipMemset(c->pub_arrivals, 0, sizeof(int) * 4));
-    RC(dalloc(c, &c->T_row_fix, M));
-    HIPCHK(c, hipMemset(c->T_row_fix, 0, sizeof(int) * M));
-    RC(dalloc(c, &c->T_row_main, M));
-    HIPCHK(c, hipMemset(c->T_row_main, 0, sizeof(int) * M));
+    RC(dalloc0(c, (char**)&c->ja, Mj * J * c->esz));
+    RC(dalloc0(c, (char**)&c->cvt_a, (size_t)M * H * c->esz)); RC(dalloc0(c, (char**)&c->cvt_b, (size_t)M * H * c->esz));
+    RC(dalloc0(c, &c->logits, Mj * V));
+    RC(dalloc0(c, &c->ds.t_idx, M)); RC(dalloc0(c, &c->ds.iters, M)); RC(dalloc0(c, &c->ds.token, Md));
+    RC(dalloc0(c, &c->ds.emit, Md)); RC(dalloc0(c, &c->ds.logp_sum, M));
+    RC(dalloc0(c, &c->ds.sum_iters, M)); RC(dalloc0(c, &c->ds.n_ones, M)); RC(dalloc0(c, &c->zero_rows, M));
+    RC(dalloc0(c, &c->pub_arrivals, 4));
+    RC(dalloc0(c, &c->T_row_fix, M));
+    RC(dalloc0(c, &c->T_row_main, M));
     // measured (profiles/r03/r03_experiments.txt I): host time per model step 66 -> 45 us, but the replay starts its first cell ~6 us
     // later than a plain launch does: f32 -2 % (52.8 against 54.0 k audio-s/s), bf16 +0.5 %  =>  on for bf16, off for f32
     {   // see lasr_ctx::fe_lds_pad.  The kernels' own (static) LDS is asked of the runtime, not assumed
@@ -337,8 +333,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
     if (getenv("LASR_MAIN_GRAPH")) c->main_graph = atoi(getenv("LASR_MAIN_GRAPH")) != 0;
     c->T_row_dev = c->zero_rows;
     for (int q = 0; q < lasr_ctx::NFLY; ++q) {
-        RC(dalloc(c, &c->T_row_ring[q], M));
-        HIPCHK(c, hipMemset(c->T_row_ring[q], 0, sizeof(int) * M));
+        RC(dalloc0(c, &c->T_row_ring[q], M));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_enc[q], hipEventDisableTiming));
     }
     // (round 3 measured CU masks for either stream, a high-priority decode stream and per-stream delay probes: every one of them
@@ -368,18 +363,13 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         if (getenv("LASR_VERBOSE"))
             fprintf(stderr, "[lasr] decode stream: %d stream(s) tried, overlap probe %.2f\n", c->dec_stream_attempts, c->dec_stream_ratio);
     }
-    RC(dalloc(c, &c->pe_ring, (size_t)lasr_ctx::RING * M * J));
-    HIPCHK(c, hipMemset(c->pe_ring, 0, sizeof(float) * (size_t)lasr_ctx::RING * M * J));
-    RC(dalloc(c, &c->c_cur, M)); RC(dalloc(c, &c->c_avail, M)); RC(dalloc(c, &c->c_iters, M)); RC(dalloc(c, &c->c_target, M));
-    RC(dalloc(c, &c->c_ntotal, M)); RC(dalloc(c, &c->c_enc_frames, M)); RC(dalloc(c, &c->c_enc_base, M));
-    HIPCHK(c, hipMemset(c->c_enc_base, 0, sizeof(int) * M)); RC(dalloc(c, &c->c_behind, 64));
+    RC(dalloc0(c, &c->pe_ring, (size_t)lasr_ctx::RING * M * J));
+    RC(dalloc0(c, &c->c_cur, M)); RC(dalloc0(c, &c->c_avail, M)); RC(dalloc0(c, &c->c_iters, M)); RC(dalloc0(c, &c->c_target, M));
+    RC(dalloc0(c, &c->c_ntotal, M)); RC(dalloc0(c, &c->c_enc_frames, M)); RC(dalloc0(c, &c->c_enc_base, M)); RC(dalloc0(c, &c->c_behind, 64));
     // (c_ntok_end / c_tok_ring live in pinned host memory, written by k_select directly: see below)
-    for (int* p : {c->c_cur, c->c_avail, c->c_iters, c->c_target, c->c_ntotal, c->c_enc_frames})
-        HIPCHK(c, hipMemset(p, 0, sizeof(int) * M));
-    HIPCHK(c, hipMemset(c->c_behind, 0, sizeof(int) * 64));
-    RC(dalloc(c, &c->c_done, 64)); HIPCHK(c, hipMemset(c->c_done, 0, sizeof(int) * 64));
-    RC(dalloc(c, &c->c_done2, 64)); HIPCHK(c, hipMemset(c->c_done2, 0, sizeof(int) * 64));
-    RC(dalloc(c, &c->c_iter, 4)); HIPCHK(c, hipMemset(c->c_iter, 0, sizeof(int) * 4));
+    RC(dalloc0(c, &c->c_done, 64));
+    RC(dalloc0(c, &c->c_done2, 64));
+    RC(dalloc0(c, &c->c_iter, 4));
     HIPCHK(c, hipHostMalloc((void**)&c->cont_host, sizeof(int) * (16 + (size_t)M * (lasr_ctx::NFLY + lasr_ctx::ENDSLOTS + lasr_ctx::TOKRING))));
     memset(c->cont_host, 0, sizeof(int) * (16 + (size_t)M * (lasr_ctx::NFLY + lasr_ctx::ENDSLOTS + lasr_ctx::TOKRING)));
     {   // continuous decode: the token ring and the per-step boundary marks are written by k_select straight
@@ -395,24 +385,19 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
     c->h_frames_sub.assign(M, 0); c->h_fetched.assign(M, 0); c->h_cur_seen.assign(M, 0); c->h_avail.assign(M, 0);
     c->dec_t_idx = c->ds.t_idx;
     c->T_row_dec = c->T_row_dev;
-    for (int* p : {c->ds.t_idx, c->ds.iters, c->ds.sum_iters, c->ds.n_ones})
-        HIPCHK(c, hipMemset(p, 0, sizeof(int) * M));
-    HIPCHK(c, hipMemset(c->ds.token, 0, sizeof(int) * Md)); HIPCHK(c, hipMemset(c->ds.emit, 0, sizeof(int) * Md));
-    HIPCHK(c, hipMemset(c->ds.logp_sum, 0, sizeof(double) * M));
     // (the reference front-end: 10 frames of 128 mels per stacked frame; other shapes take the per-chunk kernels)
     c->fe_fused = M <= 512 && d.n_buffer <= 4 && d.n_stack == 10 && d.n_mels <= 128 && d.feat == 1280 && !getenv("LASR_FE_LEGACY");
     c->h_ring_pos.assign(M, 0);
     c->ring_chunks = c->fe_fused ? d.n_window + d.n_buffer - 1 : d.n_window;
     c->pend_serial.assign((size_t)M * d.n_buffer, 0); c->pend_mat.assign((size_t)M * d.n_buffer, 0);
-    RC(dalloc(c, &c->win, (size_t)M * c->ring_chunks * d.chunk)); HIPCHK(c, hipMemset(c->win, 0, (size_t)M * c->ring_chunks * d.chunk * 4));
-    RC(dalloc(c, &c->ring_pos, M)); HIPCHK(c, hipMemset(c->ring_pos, 0, sizeof(int) * M));
-    RC(dalloc(c, &c->pend, (size_t)M * d.n_buffer * d.n_stack * d.n_mels));
-    HIPCHK(c, hipMemset(c->pend, 0, (size_t)M * d.n_buffer * d.n_stack * d.n_mels * 4));
+    RC(dalloc0(c, &c->win, (size_t)M * c->ring_chunks * d.chunk));
+    RC(dalloc0(c, &c->ring_pos, M));
+    RC(dalloc0(c, &c->pend, (size_t)M * d.n_buffer * d.n_stack * d.n_mels));
 
     lasr_ctx::Cmd tmp;
     c->cmd_bytes = cmd_layout(tmp, nullptr, M);
     HIPCHK(c, hipHostMalloc((void**)&c->cmd_host, c->cmd_bytes * NCMD));
-    RC(dalloc(c, &c->cmd_dev, c->cmd_bytes * NCMD)); HIPCHK(c, hipMemset(c->cmd_dev, 0, c->cmd_bytes * NCMD));
+    RC(dalloc0(c, &c->cmd_dev, c->cmd_bytes * NCMD));
     RC(ensure_T(c, std::max(d.n_buffer, 4)));
 
     // ---- predictor input tables (one-time, on device, always exact f32: the table is f32 in both
@@ -425,7 +410,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
             pack_tiles(pk, 0, H / 16, E, [&](int t, int ui, int k) { return ffn_w[(size_t)(16 * t + ui) * E + k]; });
             RC(upload_packed(c, &wf, pk)); RC(upload(c, &bfn, ffn_b, H));
             RC(dalloc(c, &EF, (size_t)V * H));
-            GemmArgs g{}; g.A[0] = emb_dev; g.a_mt_total[0] = E; g.a_mt_off[0] = 0; g.KC[0] = E / 16; g.W[0] = wf; g.a_rows = V;
+            GemmArgs g{}; set_operand(g, 0, emb_dev, E, 0, E / 16, wf); g.a_rows = V;
             EpiLinear::Args ea{}; ea.bias = bfn; ea.out = EF; ea.ldo = H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
             launch_table_gemm_f32(c, H / 16, V / 16, g, ea);
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -438,7 +423,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         pack_tiles(pk, 0, G * H / 16, H, [&](int t, int ui, int k) { return in0_w[(size_t)(16 * t + ui) * H + k]; });
         RC(upload_packed(c, &wt, pk)); RC(upload(c, &bt, in0_b.data(), in0_b.size()));
         RC(dalloc(c, &c->pred[0].tab, (size_t)V * G * H));
-        GemmArgs g{}; g.A[0] = EF; g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.KC[0] = H / 16; g.W[0] = wt; g.a_rows = V;
+        GemmArgs g{}; set_operand(g, 0, EF, H, 0, H / 16, wt); g.a_rows = V;
         EpiLinear::Args ea{}; ea.bias = bt; ea.out = c->pred[0].tab; ea.ldo = G * H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
         launch_table_gemm_f32(c, G * H / 16, V / 16, g, ea);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -467,11 +452,11 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         for (int l = 0; l < d.pred_layers; ++l) {
             RC(dalloc(c, &c->bos_h[l], H));
             if (d.pred_cell) RC(dalloc(c, &c->bos_c[l], H));
-            b.pred_h[l] = c->pred_h[c->pred_par][l]; b.pred_c[l] = d.pred_cell ? c->pred_c[l] : nullptr;
+            b.pred_h[l] = c->pred_h[c->pred_par][l]; b.pred_c[l] = d.pred_cell ? c->pred_c[0][l] : nullptr;
             b.bos_h[l] = c->bos_h[l]; b.bos_c[l] = c->bos_c[l];
         }
         RC(dalloc(c, &c->bos_pp, J));
-        b.pp = c->pp; b.bos_pp = c->bos_pp;
+        b.pp = c->pp[0]; b.bos_pp = c->bos_pp;
         hipLaunchKernelGGL(k_bos_capture, dim3(grid1(std::max(H, J))), dim3(256), 0, c->stream, b);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
@@ -503,7 +488,6 @@ int lasr_create(int device, const lasr_model_desc* d, const float* weights, size
 }
 
 // ---------------------------------------------------------------------------- slots
-static void cont_poll(lasr_ctx* c);
 
 int lasr_stream_open(lasr_ctx* c, int* slot) {
     if (!c || !slot) return LASR_EINVAL;
@@ -598,8 +582,6 @@ int lasr_stream_close(lasr_ctx* c, int slot) {
 }
 
 // ---------------------------------------------------------------------------- streaming
-static int cont_pump(lasr_ctx* c, int G);
-static void cont_poll(lasr_ctx* c);
 
 static void fill_mel_args(lasr_ctx* c, MelArgs& m) {
     const lasr_model_desc& d = c->d;
@@ -1052,10 +1034,6 @@ int lasr_step_stream(lasr_ctx* c, const int* slots, int n, int* n_ran) {
     if (n_ran) *n_ran = (int)model_rows.size();
     return LASR_OK;
 }
-
-static int cont_pump(lasr_ctx* c, int G);
-static int pump_start(lasr_ctx* c);
-static void pump_kick(lasr_ctx* c);
 
 // Pipelined + continuous form of lasr_step_stream.  submit: front-end + encoder of this chunk on the
 // main stream (the encoder half of the joint goes to a per-row frame ring).  ONE greedy loop runs on
@@ -1515,10 +1493,10 @@ static int cont_launch_group(lasr_ctx* c, int G, bool from_pump = false) {
         if (by_value) {
             AvailV av;
             for (int r = 0; r < 512; ++r) av.v[r] = r < M ? c->h_avail[r] : 0;
-            hipLaunchKernelGGL(k_ja_admit, dim3(grid1((size_t)M * J)), dim3(256), 0, sd, (const float*)pe, (const float*)c->pp,
+            hipLaunchKernelGGL(k_ja_admit, dim3(grid1((size_t)M * J)), dim3(256), 0, sd, (const float*)pe, (const float*)c->pp[0],
                                (const int*)c->c_cur, av, c->c_avail, c->ja, J, M, c->MTj, R, c->bf, la);
         } else {
-            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, sd, pe, c->pp, c->c_cur,
+            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, sd, pe, c->pp[0], c->c_cur,
                                c->c_avail, c->ja, J, M, c->MTj, R, c->bf, 1, M, la);
         }
     }
@@ -2058,7 +2036,7 @@ int lasr_predictor(lasr_ctx* c, const int32_t* tok, int B, int U, float* out) {
         HIPCHK(c, hipMemcpyAsync(c->ds.emit, c->dc.emit, sizeof(int) * c->M, hipMemcpyDeviceToDevice, c->stream));
         launch_predictor(c);
     }
-    hipLaunchKernelGGL(k_from_elem, dim3(grid1((size_t)B * H)), dim3(256), 0, c->stream, (const void*)c->pred_y[c->d.pred_layers - 1],
+    hipLaunchKernelGGL(k_from_elem, dim3(grid1((size_t)B * H)), dim3(256), 0, c->stream, (const void*)c->pred_y[0][c->d.pred_layers - 1],
                        out, (size_t)B * H, c->bf);
     HIPCHK(c, hipGetLastError());
     return LASR_OK;
@@ -2076,13 +2054,13 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
             hipLaunchKernelGGL(k_to_elem, dim3(grid1((size_t)B * H)), dim3(256), 0, c->stream, h_enc, c->cvt_b, (size_t)B * H, 1);
             ap = c->cvt_a; ae = c->cvt_b;
         }
-        GemmArgs g{}; g.A[0] = ap; g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.W[0] = c->W1p; g.a_rows = B;
-        EpiLinear::Args ea{}; ea.bias = c->b1; ea.out = c->pp; ea.ldo = J; ea.n_rows = B; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
+        GemmArgs g{}; set_operand(g, 0, ap, H, 0, 0, c->W1p); g.a_rows = B;
+        EpiLinear::Args ea{}; ea.bias = c->b1; ea.out = c->pp[0]; ea.ldo = J; ea.n_rows = B; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
         launch_linear<true, 3>(c, J / 16, (B + 15) / 16, g, H, ea);
         g.A[0] = ae; g.W[0] = c->W1e; ea.bias = nullptr; ea.out = c->pe;
         launch_linear<true, 3>(c, J / 16, (B + 15) / 16, g, H, ea);
     }
-    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)c->M * J)), dim3(256), 0, c->stream, (const float*)c->pe, (const float*)c->pp,
+    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)c->M * J)), dim3(256), 0, c->stream, (const float*)c->pe, (const float*)c->pp[0],
                        (const int*)nullptr, (const int*)nullptr, c->ja, J, c->M, c->MTj, 1 << 30, c->bf, 1, c->M, 1);
     launch_logits(c, logits, B, false);
     if (logp_max && argmax) {
@@ -2105,8 +2083,6 @@ static long long resample_num_out(long long n_in, int sr_in, int sr_out) {     /
     if (last * ticks_out == length) last -= 1;
     return last + 1;
 }
-
-int lasr_resample(lasr_ctx* c, const float* pcm, int B, int64_t N_in, int sr_in, float* out, int64_t* N_out);
 
 // Generic client windows (any chunk length, any sample rate): what ASRServicer.TranscribeStream + x_tfm_stream do per call
 // (api-server.py:83-115; transforms.py:141-144 Resample of the WHOLE window, :306-323 log-mel of the window with reflect
@@ -2327,7 +2303,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
         pack_tiles(pk, 0, 4 * H / 16, E, [&](int t, int ui, int k) { return in0_w[(size_t)(16 * t + ui) * E + k]; });
         RC(upload_packed(c, &wt, pk)); RC(upload(c, &bt, in0_b.data(), in0_b.size()));
         RC(dalloc(c, &m.cells[0].tab, (size_t)V * 4 * H));
-        GemmArgs g{}; g.A[0] = emb_dev; g.a_mt_total[0] = E; g.a_mt_off[0] = 0; g.KC[0] = E / 16; g.W[0] = wt; g.a_rows = V;
+        GemmArgs g{}; set_operand(g, 0, emb_dev, E, 0, E / 16, wt); g.a_rows = V;
         EpiLinear::Args ea{}; ea.bias = bt; ea.out = m.cells[0].tab; ea.ldo = 4 * H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
         launch_table_gemm_f32(c, 4 * H / 16, V / 16, g, ea);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2337,22 +2313,16 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
         dfree(c, m.cells[0].WxA); m.cells[0].WxA = nullptr;
     }
     for (int p = 0; p < 2; ++p) m.h[p].resize(L);
-    m.y.resize(L); m.cst.resize(L);
-    for (int l = 0; l < L; ++l) {
-        for (int p = 0; p < 2; ++p) { RC(dalloc(c, (char**)&m.h[p][l], (size_t)M * H * c->esz)); HIPCHK(c, hipMemset(m.h[p][l], 0, (size_t)M * H * c->esz)); }
-        RC(dalloc(c, (char**)&m.y[l], (size_t)M * H * c->esz)); HIPCHK(c, hipMemset(m.y[l], 0, (size_t)M * H * c->esz));
-        RC(dalloc(c, &m.cst[l], (size_t)M * H)); HIPCHK(c, hipMemset(m.cst[l], 0, sizeof(float) * (size_t)M * H));
-    }
-    RC(dalloc(c, &m.raw, (size_t)M * V)); RC(dalloc(c, &m.lmz, (size_t)M * V)); RC(dalloc(c, &m.valid, M));
-    HIPCHK(c, hipMemset(m.lmz, 0, sizeof(float) * (size_t)M * V)); HIPCHK(c, hipMemset(m.valid, 0, sizeof(int) * M));
-    if (c->W > 1) {                                    // second parity of everything a re-parented slot inherits
-        m.y1.assign(L, nullptr); m.cst1.assign(L, nullptr);
+    for (int l = 0; l < L; ++l)
+        for (int p = 0; p < 2; ++p) RC(dalloc0(c, (char**)&m.h[p][l], (size_t)M * H * c->esz));
+    RC(dalloc(c, &m.raw, (size_t)M * V));
+    for (int p = 0; p < (c->W > 1 ? 2 : 1); ++p) {     // beam: second parity of everything a re-parented slot inherits
+        m.y[p].assign(L, nullptr); m.cst[p].assign(L, nullptr);
         for (int l = 0; l < L; ++l) {
-            RC(dalloc(c, (char**)&m.y1[l], (size_t)M * H * c->esz)); HIPCHK(c, hipMemset(m.y1[l], 0, (size_t)M * H * c->esz));
-            RC(dalloc(c, &m.cst1[l], (size_t)M * H)); HIPCHK(c, hipMemset(m.cst1[l], 0, sizeof(float) * (size_t)M * H));
+            RC(dalloc0(c, (char**)&m.y[p][l], (size_t)M * H * c->esz));
+            RC(dalloc0(c, &m.cst[p][l], (size_t)M * H));
         }
-        RC(dalloc(c, &m.lmz1, (size_t)M * V)); RC(dalloc(c, &m.valid1, M));
-        HIPCHK(c, hipMemset(m.lmz1, 0, sizeof(float) * (size_t)M * V)); HIPCHK(c, hipMemset(m.valid1, 0, sizeof(int) * M));
+        RC(dalloc0(c, &m.lmz[p], (size_t)M * V)); RC(dalloc0(c, &m.valid[p], M));
     }
     for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);   // decode groups change shape
     c->graphs.clear();
@@ -2361,7 +2331,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
     if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;
-    c->ds.lmz = m.lmz; c->ds.lm_valid = m.valid; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
+    c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
     m.on = true;
     RC(lm_side_setup(c));
     return LASR_OK;
@@ -2439,25 +2409,24 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
         dfree(c, emb_dev); dfree(c, qa); dfree(c, sx);
     }
     for (int p = 0; p < 2; ++p) m.h[p].resize(L);
-    m.y.assign(L, nullptr); m.cst.resize(L);
+    m.y[0].assign(L, nullptr); m.cst[0].resize(L);
     for (int l = 0; l < L; ++l) {
         float* h = nullptr;
-        RC(dalloc(c, &h, (size_t)M * H)); HIPCHK(c, hipMemset(h, 0, sizeof(float) * (size_t)M * H));
+        RC(dalloc0(c, &h, (size_t)M * H));
         m.h[0][l] = m.h[1][l] = h;                              // row-local in-place update: no ping-pong
-        RC(dalloc(c, &m.cst[l], (size_t)M * H)); HIPCHK(c, hipMemset(m.cst[l], 0, sizeof(float) * (size_t)M * H));
+        RC(dalloc0(c, &m.cst[0][l], (size_t)M * H));
     }
     m.qh.assign(L, nullptr); m.sxh.assign(L, nullptr);
     {   // quantised image of h = 0: zeros with scale 0.1 (what ChooseQuantizationParams makes of an all-zero row)
         std::vector<float> tenth(M, 0.1f);
         for (int l = 0; l < L; ++l) {
-            RC(dalloc(c, &m.qh[l], (size_t)M * m.Kp_h)); HIPCHK(c, hipMemset(m.qh[l], 0, sizeof(unsigned short) * (size_t)M * m.Kp_h));
+            RC(dalloc0(c, &m.qh[l], (size_t)M * m.Kp_h));
             RC(upload(c, &m.sxh[l], tenth.data(), (size_t)M));
         }
     }
     RC(dalloc(c, &m.gx, (size_t)M * 4 * H)); RC(dalloc(c, &m.gh, (size_t)M * 4 * H));
     RC(dalloc(c, &m.qa, (size_t)M * Kmax)); RC(dalloc(c, &m.sx, M));
-    RC(dalloc(c, &m.raw, (size_t)M * V)); RC(dalloc(c, &m.lmz, (size_t)M * V)); RC(dalloc(c, &m.valid, M));
-    HIPCHK(c, hipMemset(m.lmz, 0, sizeof(float) * (size_t)M * V)); HIPCHK(c, hipMemset(m.valid, 0, sizeof(int) * M));
+    RC(dalloc(c, &m.raw, (size_t)M * V)); RC(dalloc0(c, &m.lmz[0], (size_t)M * V)); RC(dalloc0(c, &m.valid[0], M));
     for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);   // decode groups change shape
     c->graphs.clear();
     for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
@@ -2465,7 +2434,7 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
     if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;
-    c->ds.lmz = m.lmz; c->ds.lm_valid = m.valid; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
+    c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
     m.q8 = true;
     m.on = true;
     RC(lm_side_setup(c));
@@ -2828,8 +2797,7 @@ int lasr_bench_neighbour(lasr_ctx* c, int kind, int n_wg, int ms, double* rate) 
         if (!c->stream_nb) return fail(c, LASR_EHIP, "no hardware queue left for the neighbour stream");
         RC(dalloc(c, &c->nb_done, 4096));
         c->nb_floats = (size_t)128 << 20;                 // 512 MB: twice the Infinity Cache
-        RC(dalloc(c, &c->nb_buf, c->nb_floats));
-        HIPCHK(c, hipMemset(c->nb_buf, 0, sizeof(float) * c->nb_floats));
+        RC(dalloc0(c, &c->nb_buf, c->nb_floats));
         HIPCHK(c, hipDeviceSynchronize());
     }
     HIPCHK(c, hipMemsetAsync(c->nb_done, 0, sizeof(unsigned long long) * 4096, c->stream_nb));

@@ -117,6 +117,10 @@ struct GemmArgs {
     int prio;                // wave priority for the whole kernel (s_setprio 0..3): 1 for the decode-stream GEMMs, 0 otherwise
     int skip_idle;           // COMPACT: an m-group without a compacted row returns at once (its rows' carry is done by k_beam_carry)
 };
+// host: operand i of a launch (KC 0 where the launch helper sets it from K)
+inline void set_operand(GemmArgs& g, int i, const void* A, int a_mt_total, int a_mt_off, int KC, const void* W) {
+    g.A[i] = A; g.a_mt_total[i] = a_mt_total; g.a_mt_off[i] = a_mt_off; g.KC[i] = KC; g.W[i] = W;
+}
 
 // beam search: physical row of the parent hypothesis of row r (W slots per stream, contiguous)
 __device__ __forceinline__ int beam_prow(const int* parent, int W, int r) { return (r / W) * W + parent[r]; }
@@ -465,13 +469,13 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(const GemmArgs g, const typena
 // and cell (l + 1, t - 1) depend on nothing of each other, so the cells of an anti-diagonal share a launch and its fixed
 // costs (launch gap, prologue, LDS reduction, epilogue overlap the other cells' K loops).
 constexpr int NPMAX = 8;
-template <class Epi>
+template <class EpiArgs>
 struct MultiArgs {
     GemmArgs g[NPMAX];
-    typename Epi::Args ea[NPMAX];
+    EpiArgs ea[NPMAX];
 };
 template <class Ops, class Epi, int MT, int NW, bool AROW, int D>
-__global__ __launch_bounds__(NW * 64) void k_gemm_multi(const MultiArgs<Epi> m) {
+__global__ __launch_bounds__(NW * 64) void k_gemm_multi(const MultiArgs<typename Epi::Args> m) {
     constexpr int NT = Epi::NT, ROWS = MT * 16, LD = NT * 16 + 1;
     __shared__ float red[NW * ROWS * LD];
     __shared__ int row_map[Epi::COMPACT ? 1024 : 1];
@@ -521,6 +525,31 @@ __device__ __forceinline__ bool any16(bool flag, int lane) {
 // PRED (COMPACT): row-major state [M][H]; the rows that emitted advance; phase X is the per-token
 // table tab[token][4H] when TABLE.
 // Each workgroup tile has exactly ROWS*U = 256 (row, unit) items: one per thread.
+struct LstmArgs {
+    const float* bias;     // [4H] = b_ih + b_hh (folded into tab when TABLE)
+    const float* tab;      // [V][4H]
+    const int* token;      // [M]
+    const int* flag;       // ENC: T_row[M];  PRED: emit[M]
+    int t;                 // ENC: time step
+    unsigned long long tile_mask;   // ENC: bit mt set iff m-tile mt has a row with t < T_row (host-computed:
+                           //      no global load sits in front of the first weight load)
+    float* c;              // [H][M] cell state (f32), in place (beam: the OTHER parity, see c_in)
+    const void* h_in;      // current parity
+    void* h_out;           // other parity
+    void* y;               // BN(h'); ENC fragment-major (may be nullptr), PRED row-major
+    int y_mt_total, y_mt_off;
+    const float* bn_s;
+    const float* bn_t;
+    int H, M, MT;
+    // beam search (PRED, W > 1): every hypothesis slot may be re-parented each round, so c and y
+    // ping-pong like h, old state is read from the parent's slot and rows that are not extended
+    // carry (h, c, y) of their parent into their own slot of the other parity
+    const int* parent;
+    int W;
+    const float* c_in;
+    const void* y_in;
+    int no_carry;          // beam: the rows that are not extended have been carried by k_beam_carry
+};
 template <class Ops, bool PRED, bool TABLE, int U>
 struct EpiLSTM {
     static constexpr int NT = U / 4;                       // 4 gates x U units = NT 16-column tiles
@@ -528,31 +557,7 @@ struct EpiLSTM {
     static constexpr int PH1_TILES = (1 << NT) - 1;
     static constexpr int PH0_DEAD = -1, PH1_DEAD = -1;
     static constexpr bool COMPACT = PRED;
-    struct Args {
-        const float* bias;     // [4H] = b_ih + b_hh (folded into tab when TABLE)
-        const float* tab;      // [V][4H]
-        const int* token;      // [M]
-        const int* flag;       // ENC: T_row[M];  PRED: emit[M]
-        int t;                 // ENC: time step
-        unsigned long long tile_mask;   // ENC: bit mt set iff m-tile mt has a row with t < T_row (host-computed:
-                               //      no global load sits in front of the first weight load)
-        float* c;              // [H][M] cell state (f32), in place (beam: the OTHER parity, see c_in)
-        const void* h_in;      // current parity
-        void* h_out;           // other parity
-        void* y;               // BN(h'); ENC fragment-major (may be nullptr), PRED row-major
-        int y_mt_total, y_mt_off;
-        const float* bn_s;
-        const float* bn_t;
-        int H, M, MT;
-        // beam search (PRED, W > 1): every hypothesis slot may be re-parented each round, so c and y
-        // ping-pong like h, old state is read from the parent's slot and rows that are not extended
-        // carry (h, c, y) of their parent into their own slot of the other parity
-        const int* parent;
-        int W;
-        const float* c_in;
-        const void* y_in;
-        int no_carry;          // beam: the rows that are not extended have been carried by k_beam_carry
-    };
+    using Args = LstmArgs;
     struct Pre {
         int r;                 // row this thread finishes (-1: none)
         bool carry;            // PRED: this thread carries h of original row vr (did not emit)
@@ -634,7 +639,7 @@ struct EpiLSTMe {
     static constexpr int PH0_TILES = (1 << NT) - 1, PH1_TILES = (1 << NT) - 1;
     static constexpr int PH0_DEAD = -1, PH1_DEAD = -1;
     static constexpr bool COMPACT = false;
-    using Args = typename EpiLSTM<Ops, false, false, 8>::Args;
+    using Args = LstmArgs;
     struct Pre {};
     __device__ static bool tile_active(const Args& a, int mt, int lane) { return (a.tile_mask >> mt) & 1ull; }
     template <int MTB>
@@ -667,6 +672,23 @@ struct EpiLSTMe {
 // Pseudo-gates {z, r, gx, gh} in one 16-column tile (4 units): the x phase feeds z,r,gx (gh columns
 // dead), the h phase z,r,gh (gx dead).  TABLE: Wx (+ input bias) comes from tab[token][3H] and the x
 // phase is absent.
+struct NbrcArgs {
+    const float* bias;     // [3H] input bias (folded into tab when TABLE)
+    const float* rbias;    // [3H] recurrent bias
+    const float* tab;      // [V][3H]
+    const int* token;
+    const int* emit;
+    const void* h_in;      // [M][H] current parity
+    void* h_out;           // other parity
+    void* y;               // BN(h') [M][H]
+    const float* bn_s;
+    const float* bn_t;
+    int H, M;
+    const int* parent;     // beam search (W > 1): see EpiLSTM::Args
+    int W;
+    const void* y_in;
+    int no_carry;
+};
 template <class Ops, bool TABLE>
 struct EpiNBRC {
     static constexpr int U = 4;
@@ -676,23 +698,7 @@ struct EpiNBRC {
     static constexpr int PH0_DEAD = 12;   // gh columns carry no x weights
     static constexpr int PH1_DEAD = 8;    // gx columns carry no h weights
     static constexpr bool COMPACT = true;
-    struct Args {
-        const float* bias;     // [3H] input bias (folded into tab when TABLE)
-        const float* rbias;    // [3H] recurrent bias
-        const float* tab;      // [V][3H]
-        const int* token;
-        const int* emit;
-        const void* h_in;      // [M][H] current parity
-        void* h_out;           // other parity
-        void* y;               // BN(h') [M][H]
-        const float* bn_s;
-        const float* bn_t;
-        int H, M;
-        const int* parent;     // beam search (W > 1): see EpiLSTM::Args
-        int W;
-        const void* y_in;
-        int no_carry;
-    };
+    using Args = NbrcArgs;
     struct Pre {
         int r;
         bool carry;
@@ -761,7 +767,7 @@ struct EpiLSTMw {
     static constexpr int PH0_TILES = TABLE ? 0 : (1 << NTW) - 1, PH1_TILES = (1 << NTW) - 1;
     static constexpr int PH0_DEAD = -1, PH1_DEAD = -1;
     static constexpr bool COMPACT = true;
-    using Args = typename EpiLSTM<Ops, true, TABLE, 4>::Args;
+    using Args = LstmArgs;
     struct Pre {};
     template <int MTB>
     __device__ static __forceinline__ Pre prefetch(const Args&, int, int, int, int, const int*) { return Pre{}; }
@@ -809,7 +815,7 @@ struct EpiNBRCw {
     static constexpr int PH0_TILES = TABLE ? 0 : (1 << NTW) - 1, PH1_TILES = (1 << NTW) - 1;
     static constexpr int PH0_DEAD = 12, PH1_DEAD = 8;
     static constexpr bool COMPACT = true;
-    using Args = typename EpiNBRC<Ops, TABLE>::Args;
+    using Args = NbrcArgs;
     struct Pre {};
     template <int MTB>
     __device__ static __forceinline__ Pre prefetch(const Args&, int, int, int, int, const int*) { return Pre{}; }
@@ -852,25 +858,26 @@ struct EpiNBRCw {
 // ---- plain linear: out[row][col] = acc + bias[col], row-major f32.  NTW n-tiles (16 * NTW columns) per workgroup: 1 for the
 // skinny problems (every weight byte fetched once per m-group), 4 for hundreds of rows (beam search: 1024 hypothesis rows x
 // 1536 -- with 16-column workgroups the ACTIVATIONS are what moves, 128 n-groups x 3 MB = 400 MB through L2 per launch).
+struct LinearArgs {
+    const float* bias;    // may be nullptr
+    float* out;
+    int ldo;
+    int n_rows;           // rows >= n_rows are not written
+    const int* t_idx;     // optional row gate: row active iff t_idx[r % M] < T_row[r % M]
+    const int* T_row;
+    int M;
+    const int* ring_base; // optional: GEMM row (t*M + r) is written to row ((ring_base[r] + t) % ring)*M + r
+    int ring;
+    int W;                // beam search: row r belongs to stream r / W (t_idx, T_row are per stream)
+    const float* row_scale;   // optional (int8-served LM): out = acc * (row_scale[r] * w_scale) + bias
+    float w_scale;
+};
 template <int NTW>
 struct EpiLinearT {
     static constexpr int NT = NTW;
     static constexpr int PH0_TILES = (1 << NTW) - 1, PH1_TILES = 0, PH0_DEAD = -1, PH1_DEAD = -1;
     static constexpr bool COMPACT = false;
-    struct Args {
-        const float* bias;    // may be nullptr
-        float* out;
-        int ldo;
-        int n_rows;           // rows >= n_rows are not written
-        const int* t_idx;     // optional row gate: row active iff t_idx[r % M] < T_row[r % M]
-        const int* T_row;
-        int M;
-        const int* ring_base; // optional: GEMM row (t*M + r) is written to row ((ring_base[r] + t) % ring)*M + r
-        int ring;
-        int W;                // beam search: row r belongs to stream r / W (t_idx, T_row are per stream)
-        const float* row_scale;   // optional (int8-served LM): out = acc * (row_scale[r] * w_scale) + bias
-        float w_scale;
-    };
+    using Args = LinearArgs;
     __device__ static bool row_on(const Args& a, int r) {
         if (r >= a.n_rows) return false;
         if (!a.t_idx) return true;
@@ -914,29 +921,30 @@ using EpiLinear = EpiLinearT<1>;
 // Joint.forward 'concat' (models.py:132-140): Linear(cat(pred, enc)) == W1p pred + W1e enc + b1.
 // Workgroup (jb, mg) refreshes ja for its compacted (emitting) rows and for the NON-emitting rows
 // of the original row range [mg*ROWS, (mg+1)*ROWS).
+struct PpjArgs {
+    const float* b1;
+    float* pp;            // [M][J] f32 (beam: the other parity, see pp_in)
+    const float* pe;      // [ring][M_enc][J] f32
+    const int* t_idx;     // per stream
+    const int* T_row;
+    const int* emit;
+    void* ja;             // fragment-major [J/KCH][MT][64][16 B]
+    int J, M, MT;
+    int ring;             // pe holds frame t of row r at slot t % ring (ring >= frames of a step)
+    // beam search (W > 1): rows are hypothesis slots, W per stream; a slot that was not extended
+    // takes pp of its parent slot (current parity) into its own slot of the other parity
+    const int* parent;
+    int W, M_enc;
+    const float* pp_in;
+    int la;               // greedy lookahead: ja is also produced for frames t+1 .. t+la-1 (rows k*M + r)
+    int no_carry;         // beam: pp / ja of the rows that are not extended are done by k_beam_carry
+};
 template <class Ops, int NTW = 1>
 struct EpiPPJ {
     static constexpr int NT = NTW;
     static constexpr int PH0_TILES = (1 << NTW) - 1, PH1_TILES = 0, PH0_DEAD = -1, PH1_DEAD = -1;
     static constexpr bool COMPACT = true;
-    struct Args {
-        const float* b1;
-        float* pp;            // [M][J] f32 (beam: the other parity, see pp_in)
-        const float* pe;      // [ring][M_enc][J] f32
-        const int* t_idx;     // per stream
-        const int* T_row;
-        const int* emit;
-        void* ja;             // fragment-major [J/KCH][MT][64][16 B]
-        int J, M, MT;
-        int ring;             // pe holds frame t of row r at slot t % ring (ring >= frames of a step)
-        // beam search (W > 1): rows are hypothesis slots, W per stream; a slot that was not extended
-        // takes pp of its parent slot (current parity) into its own slot of the other parity
-        const int* parent;
-        int W, M_enc;
-        const float* pp_in;
-        int la;               // greedy lookahead: ja is also produced for frames t+1 .. t+la-1 (rows k*M + r)
-        int no_carry;         // beam: pp / ja of the rows that are not extended are done by k_beam_carry
-    };
+    using Args = PpjArgs;
     struct Pre {};
     template <int MTB>
     __device__ static __forceinline__ Pre prefetch(const Args&, int, int, int, int, const int*) { return Pre{}; }

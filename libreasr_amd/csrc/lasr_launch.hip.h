@@ -95,7 +95,7 @@ inline void launch_ppj(lasr_ctx* c, bool beam = false) {
     if (c->bf) launch_ppj_t<OpsBF16>(c, beam);
     else launch_ppj_t<OpsF32>(c, beam);
 }
-inline float* cur_pp(lasr_ctx* c) { return (c->W > 1 && c->pred_par) ? c->pp1 : c->pp; }
+inline float* cur_pp(lasr_ctx* c) { return c->pp[par_rd(c->W > 1, c->pred_par)]; }
 inline void launch_lm(lasr_ctx* c, bool beam = false, int l0 = 0, int l1 = -1, bool tail = true) {
     if (!c->lm.on) return;
     if (c->lm.q8) { launch_lm_q8(c); return; }
@@ -110,9 +110,9 @@ inline void launch_pair(lasr_ctx* c, int kind, bool lm_first, lasr_ctx::Captured
     const bool ok = c->bf ? launch_pair_ops<OpsBF16>(c, kind, lm_first, A, B) : launch_pair_ops<OpsF32>(c, kind, lm_first, A, B);
     if (!ok) { replay_captured(c, A); replay_captured(c, B); }
 }
-// current-parity LM output of the hypothesis slots (beam): parity 0 = lmz / valid, parity 1 = lmz1 / valid1
-inline const float* cur_lmz(lasr_ctx* c) { return (c->W > 1 && c->lm.par) ? c->lm.lmz1 : c->lm.lmz; }
-inline const int* cur_lm_valid(lasr_ctx* c) { return (c->W > 1 && c->lm.par) ? c->lm.valid1 : c->lm.valid; }
+// current-parity LM output of the hypothesis slots (beam)
+inline const float* cur_lmz(lasr_ctx* c) { return c->lm.lmz[par_rd(c->W > 1, c->lm.par)]; }
+inline const int* cur_lm_valid(lasr_ctx* c) { return c->lm.valid[par_rd(c->W > 1, c->lm.par)]; }
 // plain linear over element-typed A (fragment-major, or row-major when AROW); f32 row-major output
 template <bool AROW, int D>
 inline void launch_linear(lasr_ctx* c, int n_groups, int m_groups, GemmArgs g, int K, const EpiLinear::Args& ea) {

@@ -18,16 +18,16 @@ static bool launch_pair_t(lasr_ctx* c, lasr_ctx::Captured& A, lasr_ctx::Captured
 }
 
 
-static void fill_beam_carry(lasr_ctx* c, BeamCarryArgs& a) {
+static void fill_beam_carry(lasr_ctx* c, BeamCarryArgs& a) {      // (beam only: every buffer from parity p to p ^ 1)
     const int H = c->d.hidden, p = c->pred_par;
     a.emit = c->ds.emit; a.parent = c->b_parent; a.W = c->W; a.Md = c->Md; a.H = H; a.J = c->d.joint; a.Lp = c->d.pred_layers;
     a.bf = c->bf; a.lstm = c->d.pred_cell;
     for (int l = 0; l < a.Lp; ++l) {
         a.h_in[l] = c->pred_h[p][l]; a.h_out[l] = c->pred_h[p ^ 1][l];
-        a.y_in[l] = p ? c->pred_y1[l] : c->pred_y[l]; a.y_out[l] = p ? c->pred_y[l] : c->pred_y1[l];
-        if (a.lstm) { a.c_in[l] = p ? c->pred_c1[l] : c->pred_c[l]; a.c_out[l] = p ? c->pred_c[l] : c->pred_c1[l]; }
+        a.y_in[l] = c->pred_y[p][l]; a.y_out[l] = c->pred_y[p ^ 1][l];
+        if (a.lstm) { a.c_in[l] = c->pred_c[p][l]; a.c_out[l] = c->pred_c[p ^ 1][l]; }
     }
-    a.pp_in = p ? c->pp1 : c->pp; a.pp_out = p ? c->pp : c->pp1;
+    a.pp_in = c->pp[p]; a.pp_out = c->pp[p ^ 1];
     a.pe = c->pe; a.t_idx = c->dec_t_idx; a.T_row = c->T_row_dec; a.ja = c->ja; a.MTj = c->MTj; a.ring = c->pe_ring_R; a.M_enc = c->M;
 }
 // carry blocks of a launch: Md slot blocks + (LSTM predictor) the cell-state blocks
@@ -67,7 +67,7 @@ template <class Ops>
 void launch_logits_ops(lasr_ctx* c, float* out, int n_rows, bool gated) {
     const int J = c->d.joint, V = c->d.vocab;
     GemmArgs g{};
-    g.A[0] = c->ja; g.a_mt_total[0] = c->MTj; g.a_mt_off[0] = 0; g.W[0] = c->W2; g.M = c->Md;
+    set_operand(g, 0, c->ja, c->MTj, 0, 0, c->W2); g.M = c->Md;
     g.dbg = (c->dbg && c->dbg_gate) ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;
     EpiLinear::Args ea{};
     ea.bias = c->b2; ea.out = out; ea.ldo = V; ea.n_rows = n_rows;
@@ -75,10 +75,7 @@ void launch_logits_ops(lasr_ctx* c, float* out, int n_rows, bool gated) {
     if (n_rows >= 512 && V % 64 == 0) {      // 64 x 64 workgroups for the beam's hundreds of hypothesis rows (round 4: logits 28 -> 20 us)
         GemmArgs g4 = g;
         g4.KC[0] = J / Ops::KCH;
-        EpiLinearT<4>::Args e4{};
-        static_assert(sizeof(e4) == sizeof(ea), "same Args layout");
-        memcpy((void*)&e4, (const void*)&ea, sizeof(e4));
-        launch_gemm<typename WideOps<Ops>::type, EpiLinearT<4>, 4, false, -1, 4>(c, V / 64, (n_rows + 63) / 64, g4, e4);
+        launch_gemm<typename WideOps<Ops>::type, EpiLinearT<4>, 4, false, -1, 4>(c, V / 64, (n_rows + 63) / 64, g4, ea);
         return;
     }
     if (c->logits_mt == 4 || (c->logits_mt == 2 && n_rows >= 512)) { launch_logits_t<Ops, 4>(c, g, n_rows, J, ea); return; }
@@ -86,14 +83,21 @@ void launch_logits_ops(lasr_ctx* c, float* out, int n_rows, bool gated) {
     launch_linear_ops<Ops, false, -1>(c, V / 16, (n_rows + 15) / 16, g, J, ea);
 }
 
-// launch of a wide tiling through its own operand type (WideOps): the epilogue's Args are the same struct under another template
-// argument -- copied bit for bit
-template <class OW, class Epi, class ArgsIn>
-static void launch_wide(lasr_ctx* c, int n_groups, int m_groups, const GemmArgs& g, const ArgsIn& ea_in) {
-    typename Epi::Args ea;
-    static_assert(sizeof(ea) == sizeof(ea_in), "same Args layout");
-    memcpy((void*)&ea, (const void*)&ea_in, sizeof(ea));
-    launch_gemm<OW, Epi, MTA, true, -1, 4>(c, n_groups, m_groups, g, ea);
+// a predictor / LM cell in the tiling its row count asks for: 4 units per workgroup, 8 (wide8) or 16 through the wide tilings'
+// operand type (wide); TABLE: the x phase is the per-token table (layer 0)
+template <class Ops, bool TABLE>
+static void launch_lstm_cell(lasr_ctx* c, bool wide8, bool wide, int H, int mgroups, const GemmArgs& g, const LstmArgs& ea) {
+    using OW = typename WideOps<Ops>::type;            // the wide tilings' matrix instruction (see OpsBF16k16)
+    if (wide8) launch_gemm<Ops, EpiLSTMw<Ops, TABLE, 2>, MTA, true, -1>(c, H / 8, mgroups, g, ea);
+    else if (wide) launch_gemm<OW, EpiLSTMw<OW, TABLE>, MTA, true, -1, 4>(c, H / 16, mgroups, g, ea);
+    else launch_gemm<Ops, EpiLSTM<Ops, true, TABLE, 4>, MTA, true, -1>(c, H / 4, mgroups, g, ea);
+}
+template <class Ops, bool TABLE>
+static void launch_nbrc_cell(lasr_ctx* c, bool wide8, bool wide, int H, int mgroups, const GemmArgs& g, const NbrcArgs& ea) {
+    using OW = typename WideOps<Ops>::type;
+    if (wide8) launch_gemm<Ops, EpiNBRCw<Ops, TABLE, 2>, MTA, true, -1>(c, H / 8, mgroups, g, ea);
+    else if (wide) launch_gemm<OW, EpiNBRCw<OW, TABLE>, MTA, true, -1, 4>(c, H / 16, mgroups, g, ea);
+    else launch_gemm<Ops, EpiNBRC<Ops, TABLE>, MTA, true, -1>(c, H / 4, mgroups, g, ea);
 }
 
 // one predictor pass (all layers) for rows with emit != 0 (compacted inside the kernels); predictor
@@ -104,11 +108,10 @@ void launch_predictor_t(lasr_ctx* c, bool beam, int l0, int l1) {
     const int H = c->d.hidden;
     if (l1 < 0) l1 = c->d.pred_layers;
     const int mgroups = c->Md / (16 * MTA);
-    const int p = c->pred_par;
+    const int p = c->pred_par, rd = par_rd(beam, p), wr = par_wr(beam, p);   // h: p -> p ^ 1; y, c: rd -> wr
     // many decoder rows (beam 8 x 64+ streams, >= 512 streams): 16-unit workgroups, a quarter of the activation traffic
     // (configs[4], 1024 rows: predictor cells 135 -> ~50 us, whole job +60 %; at 256 rows: bf16 equal, f32 -22 %; at 64: -20 %)
     const bool wide = c->Md >= 512;
-    using OW = typename WideOps<Ops>::type;            // the wide tilings' matrix instruction (see OpsBF16k16)
     const bool wide8 = c->bf && c->Md >= 256 && c->Md < 512;   // 8 units per workgroup, 8 waves (configs[2]: 6.4 -> 7.2 k in round 2)
     const bool split_carry = beam && beam_carry_on();
     if (split_carry && beam_carry_mode() == 1 && l0 == 0) {      // the slots that are not extended: whole-row copies by their own launch (see k_beam_carry)
@@ -120,55 +123,29 @@ void launch_predictor_t(lasr_ctx* c, bool beam, int l0, int l1) {
         const Cell& L = c->pred[l];
         GemmArgs g{};
         g.skip_idle = split_carry ? 1 : 0;
-        // beam: parity p holds the current state; everything is written to parity p ^ 1
-        void* y_out = (beam && !p) ? c->pred_y1[l] : c->pred_y[l];
-        const void* y_in = (beam && p) ? c->pred_y1[l] : c->pred_y[l];
-        if (l > 0) {
-            g.A[0] = (beam && !p) ? c->pred_y1[l - 1] : c->pred_y[l - 1];   // what layer l-1 just wrote
-            g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.KC[0] = H / Ops::KCH; g.W[0] = L.WxA;
-        }
-        g.A[1] = c->pred_h[p][l]; g.a_mt_total[1] = H; g.a_mt_off[1] = 0; g.KC[1] = H / Ops::KCH; g.W[1] = L.WhA;
+        if (l > 0) set_operand(g, 0, c->pred_y[wr][l - 1], H, 0, H / Ops::KCH, L.WxA);   // what layer l-1 just wrote
+        set_operand(g, 1, c->pred_h[p][l], H, 0, H / Ops::KCH, L.WhA);
         if (beam) { g.parent = c->b_parent; g.beam_w = c->W; }
         g.compact = c->ds.emit; g.M = c->Md; g.dbg = (c->dbg && c->dbg_gate) ? c->dbg + (size_t)(1 + std::min(l, 1)) * 4096 * 16 : nullptr;
         if (c->d.pred_cell == 1) {
-            typename EpiLSTM<Ops, true, true, 4>::Args ea{};
+            LstmArgs ea{};
             ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.flag = c->ds.emit; ea.t = 0;
-            ea.c = (beam && !p) ? c->pred_c1[l] : c->pred_c[l]; ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l];
-            ea.y = y_out; ea.y_mt_total = 0; ea.y_mt_off = 0;
+            ea.c = c->pred_c[wr][l]; ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l];
+            ea.y = c->pred_y[wr][l]; ea.y_mt_total = 0; ea.y_mt_off = 0;
             ea.bn_s = L.bn_s; ea.bn_t = L.bn_t; ea.H = H; ea.M = c->Md; ea.MT = c->MTd;
-            if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.c_in = p ? c->pred_c1[l] : c->pred_c[l]; ea.y_in = y_in; }
+            if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.c_in = c->pred_c[rd][l]; ea.y_in = c->pred_y[rd][l]; }
             ea.no_carry = split_carry ? 1 : 0;
-            if (l == 0) {
-                if (wide8) launch_gemm<Ops, EpiLSTMw<Ops, true, 2>, MTA, true, -1>(c, H / 8, mgroups, g, ea);
-                else if (wide) launch_wide<OW, EpiLSTMw<OW, true>>(c, H / 16, mgroups, g, ea);
-                else launch_gemm<Ops, EpiLSTM<Ops, true, true, 4>, MTA, true, -1>(c, H / 4, mgroups, g, ea);
-            } else {
-                typename EpiLSTM<Ops, true, false, 4>::Args eb{};
-                static_assert(sizeof(eb) == sizeof(ea), "same Args layout");
-                memcpy(&eb, &ea, sizeof(eb));
-                if (wide8) launch_gemm<Ops, EpiLSTMw<Ops, false, 2>, MTA, true, -1>(c, H / 8, mgroups, g, eb);
-                else if (wide) launch_wide<OW, EpiLSTMw<OW, false>>(c, H / 16, mgroups, g, eb);
-                else launch_gemm<Ops, EpiLSTM<Ops, true, false, 4>, MTA, true, -1>(c, H / 4, mgroups, g, eb);
-            }
+            if (l == 0) launch_lstm_cell<Ops, true>(c, wide8, wide, H, mgroups, g, ea);
+            else launch_lstm_cell<Ops, false>(c, wide8, wide, H, mgroups, g, ea);
         } else {
-            typename EpiNBRC<Ops, true>::Args ea{};
+            NbrcArgs ea{};
             ea.bias = L.bias; ea.rbias = L.rbias; ea.tab = L.tab; ea.token = c->ds.token; ea.emit = c->ds.emit;
-            ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l]; ea.y = y_out;
+            ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l]; ea.y = c->pred_y[wr][l];
             ea.bn_s = L.bn_s; ea.bn_t = L.bn_t; ea.H = H; ea.M = c->Md;
-            if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.y_in = y_in; }
+            if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.y_in = c->pred_y[rd][l]; }
             ea.no_carry = split_carry ? 1 : 0;
-            if (l == 0) {
-                if (wide8) launch_gemm<Ops, EpiNBRCw<Ops, true, 2>, MTA, true, -1>(c, H / 8, mgroups, g, ea);
-                else if (wide) launch_wide<OW, EpiNBRCw<OW, true>>(c, H / 16, mgroups, g, ea);
-                else launch_gemm<Ops, EpiNBRC<Ops, true>, MTA, true, -1>(c, H / 4, mgroups, g, ea);
-            } else {
-                typename EpiNBRC<Ops, false>::Args eb{};
-                static_assert(sizeof(eb) == sizeof(ea), "same Args layout");
-                memcpy(&eb, &ea, sizeof(eb));
-                if (wide8) launch_gemm<Ops, EpiNBRCw<Ops, false, 2>, MTA, true, -1>(c, H / 8, mgroups, g, eb);
-                else if (wide) launch_wide<OW, EpiNBRCw<OW, false>>(c, H / 16, mgroups, g, eb);
-                else launch_gemm<Ops, EpiNBRC<Ops, false>, MTA, true, -1>(c, H / 4, mgroups, g, eb);
-            }
+            if (l == 0) launch_nbrc_cell<Ops, true>(c, wide8, wide, H, mgroups, g, ea);
+            else launch_nbrc_cell<Ops, false>(c, wide8, wide, H, mgroups, g, ea);
         }
     }
     if (!beam && l1 == c->d.pred_layers) c->pred_par ^= 1;      // beam: launch_ppj (same pass, same parities) toggles
@@ -176,15 +153,15 @@ void launch_predictor_t(lasr_ctx* c, bool beam, int l0, int l1) {
 // pp (for emitting rows) and the joint activation ja = tanh(pe[t_idx] + pp) for all rows still decoding
 template <class Ops>
 void launch_ppj_t(lasr_ctx* c, bool beam) {
-    const int H = c->d.hidden, J = c->d.joint, L = c->d.pred_layers, p = c->pred_par;
+    const int H = c->d.hidden, J = c->d.joint, L = c->d.pred_layers;
+    const int rd = par_rd(beam, c->pred_par), wr = par_wr(beam, c->pred_par);
     GemmArgs g{};
-    g.A[0] = (beam && !p) ? c->pred_y1[L - 1] : c->pred_y[L - 1];      // what the predictor pass just wrote
-    g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.KC[0] = H / Ops::KCH; g.W[0] = c->W1p;
+    set_operand(g, 0, c->pred_y[wr][L - 1], H, 0, H / Ops::KCH, c->W1p);      // what the predictor pass just wrote
     g.compact = c->ds.emit; g.M = c->Md; g.dbg = (c->dbg && c->dbg_gate) ? c->dbg + (size_t)3 * 4096 * 16 : nullptr;
-    typename EpiPPJ<Ops>::Args ea{};
-    ea.b1 = c->b1; ea.pp = (beam && !p) ? c->pp1 : c->pp; ea.pe = c->pe; ea.t_idx = c->dec_t_idx; ea.T_row = c->T_row_dec; ea.emit = c->ds.emit;
+    PpjArgs ea{};
+    ea.b1 = c->b1; ea.pp = c->pp[wr]; ea.pe = c->pe; ea.t_idx = c->dec_t_idx; ea.T_row = c->T_row_dec; ea.emit = c->ds.emit;
     ea.ja = c->ja; ea.J = J; ea.M = c->Md; ea.MT = c->MTj; ea.ring = c->pe_ring_R; ea.la = beam ? 1 : c->la;
-    if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.M_enc = c->M; ea.pp_in = p ? c->pp1 : c->pp; }
+    if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.M_enc = c->M; ea.pp_in = c->pp[rd]; }
     if (beam && beam_carry_on()) { ea.no_carry = 1; g.skip_idle = 1; }      // (k_beam_carry, launched with the predictor pass)
     const bool ppj_wide = c->Md >= 512 && c->MTd % 4 == 0;   // 64-row workgroups for many decoder rows (64-column ones measured slower:
                                                              // 19.9 against 14.3 us at 1024 rows, round 4)
@@ -202,44 +179,32 @@ void launch_ppj_t(lasr_ctx* c, bool beam) {
 template <class Ops>
 void launch_lm_t(lasr_ctx* c, bool beam, int l0, int l1, bool tail) {
     lasr_ctx::LM& m = c->lm;
-    const int H = m.H, V = c->d.vocab, p = m.par;
-    const int R = beam ? c->Md : c->M;                   // LM rows: streams, or hypothesis slots (beam: parity p -> p ^ 1, parent-indirected)
+    const int H = m.H, V = c->d.vocab, p = m.par, rd = par_rd(beam, p), wr = par_wr(beam, p);   // h: p -> p ^ 1; the rest: rd -> wr
+    const int R = beam ? c->Md : c->M;                   // LM rows: streams, or hypothesis slots (beam: parent-indirected)
     if (l1 < 0) l1 = m.L;
     for (int l = l0; l < l1; ++l) {
         const Cell& L = m.cells[l];
         GemmArgs g{};
-        void* y_out = (beam && !p) ? m.y1[l] : m.y[l];
-        const void* y_in = (beam && p) ? m.y1[l] : m.y[l];
-        if (l > 0) { g.A[0] = (beam && !p) ? m.y1[l - 1] : m.y[l - 1]; g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.KC[0] = H / Ops::KCH; g.W[0] = L.WxA; }
-        g.A[1] = m.h[p][l]; g.a_mt_total[1] = H; g.a_mt_off[1] = 0; g.KC[1] = H / Ops::KCH; g.W[1] = L.WhA;
+        if (l > 0) set_operand(g, 0, m.y[wr][l - 1], H, 0, H / Ops::KCH, L.WxA);
+        set_operand(g, 1, m.h[p][l], H, 0, H / Ops::KCH, L.WhA);
         if (beam) { g.parent = c->b_parent; g.beam_w = c->W; }
         g.compact = c->ds.emit; g.M = R;
-        typename EpiLSTM<Ops, true, true, 4>::Args ea{};
+        LstmArgs ea{};
         ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.flag = c->ds.emit; ea.t = 0;
-        ea.c = (beam && !p) ? m.cst1[l] : m.cst[l]; ea.h_in = m.h[p][l]; ea.h_out = m.h[p ^ 1][l]; ea.y = y_out;
+        ea.c = m.cst[wr][l]; ea.h_in = m.h[p][l]; ea.h_out = m.h[p ^ 1][l]; ea.y = m.y[wr][l];
         ea.bn_s = m.ones; ea.bn_t = m.zeros; ea.H = H; ea.M = R; ea.MT = R / 16;
-        if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.c_in = p ? m.cst1[l] : m.cst[l]; ea.y_in = y_in; }
-        if (l == 0) {
-            launch_gemm<Ops, EpiLSTM<Ops, true, true, 4>, MTA, true, -1>(c, H / 4, R / (16 * MTA), g, ea);
-        } else {
-            typename EpiLSTM<Ops, true, false, 4>::Args eb{};
-            memcpy(&eb, &ea, sizeof(eb));
-            launch_gemm<Ops, EpiLSTM<Ops, true, false, 4>, MTA, true, -1>(c, H / 4, R / (16 * MTA), g, eb);
-        }
+        if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.c_in = m.cst[rd][l]; ea.y_in = m.y[rd][l]; }
+        if (l == 0) launch_lstm_cell<Ops, true>(c, false, false, H, R / (16 * MTA), g, ea);      // (always the 4-unit tiling)
+        else launch_lstm_cell<Ops, false>(c, false, false, H, R / (16 * MTA), g, ea);
     }
     if (l1 < m.L || !tail) return;
     GemmArgs g{};
-    g.A[0] = (beam && !p) ? m.y1[m.L - 1] : m.y[m.L - 1]; g.a_mt_total[0] = H; g.a_mt_off[0] = 0; g.W[0] = m.Wout; g.a_rows = R;
+    set_operand(g, 0, m.y[wr][m.L - 1], H, 0, 0, m.Wout); g.a_rows = R;
     EpiLinear::Args ea{};
     ea.bias = m.bout; ea.out = m.raw; ea.ldo = V; ea.n_rows = R; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = R;
     launch_linear_ops<Ops, true, -1>(c, V / 16, R / 16, g, H, ea);
-    if (beam)
-        LAUNCH_LM_POST(V, dim3(R), dim3(256), 0, c->stream, (const float*)m.raw, (const int*)c->ds.emit, p ? m.lmz : m.lmz1,
-                           p ? m.valid : m.valid1, V, m.min_val, (const int*)c->b_parent, c->W, (const float*)(p ? m.lmz1 : m.lmz),
-                           (const int*)(p ? m.valid1 : m.valid));
-    else
-        LAUNCH_LM_POST(V, dim3(R), dim3(256), 0, c->stream, (const float*)m.raw, (const int*)c->ds.emit, m.lmz, m.valid, V, m.min_val,
-                           (const int*)nullptr, 1, (const float*)m.lmz, (const int*)m.valid);
+    LAUNCH_LM_POST(V, dim3(R), dim3(256), 0, c->stream, (const float*)m.raw, (const int*)c->ds.emit, m.lmz[wr], m.valid[wr], V, m.min_val,
+                       beam ? (const int*)c->b_parent : (const int*)nullptr, beam ? c->W : 1, (const float*)m.lmz[rd], (const int*)m.valid[rd]);
     m.par ^= 1;
 }
 // the pair kinds of one operand type (see launch_pair): false = not a kind the templates name

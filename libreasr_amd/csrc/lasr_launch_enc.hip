@@ -8,8 +8,8 @@ static void launch_enc_cell_t(lasr_ctx* c, int l, int t, const void* xsrc, int x
     const Cell& L = c->enc[l];
     const int H = c->d.hidden;
     GemmArgs g{};
-    g.A[0] = xsrc; g.a_mt_total[0] = x_mt_total; g.a_mt_off[0] = t * c->MT; g.KC[0] = L.I / Ops::KCH; g.W[0] = L.WxC;
-    g.A[1] = c->enc_h[c->enc_par][l]; g.a_mt_total[1] = c->MT; g.a_mt_off[1] = 0; g.KC[1] = H / Ops::KCH; g.W[1] = L.WhC;
+    set_operand(g, 0, xsrc, x_mt_total, t * c->MT, L.I / Ops::KCH, L.WxC);
+    set_operand(g, 1, c->enc_h[c->enc_par][l], c->MT, 0, H / Ops::KCH, L.WhC);
     g.M = c->M; g.dbg = c->dbg;
     if (c->cell_prof && c->cp_slots && c->cp_slot_next < lasr_ctx::NCELLSLOT) {
         c->cp_slot_cells[c->cp_slot_next] = 1;
@@ -18,7 +18,7 @@ static void launch_enc_cell_t(lasr_ctx* c, int l, int t, const void* xsrc, int x
         c->cp_slot_next++;
     }
     using E = EpiLSTM<Ops, false, false, 8>;
-    typename E::Args ea{};
+    LstmArgs ea{};
     ea.bias = L.bias; ea.flag = c->T_row_dev; ea.t = t; ea.tile_mask = c->tile_masks.empty() ? ~0ull : c->tile_masks[t];
     ea.c = c->enc_c[l]; ea.h_in = c->enc_h[c->enc_par][l]; ea.h_out = c->enc_h[c->enc_par ^ 1][l];
     ea.y = ydst; ea.y_mt_total = y_mt_total; ea.y_mt_off = t * c->MT;
@@ -28,11 +28,8 @@ static void launch_enc_cell_t(lasr_ctx* c, int l, int t, const void* xsrc, int x
     const int nw = c->cell_nw ? c->cell_nw : (Ops::BF ? 8 : 4);
     if (c->enc_u12) {
         using E12 = EpiLSTMe<Ops, 12>;
-        typename E12::Args e12;
-        static_assert(sizeof(e12) == sizeof(ea), "same Args layout");
-        memcpy((void*)&e12, (const void*)&ea, sizeof(e12));
-        if (c->cell_nw == 4) launch_gemm<Ops, E12, 4, false, 3, 4>(c, H / 12, c->M / 64, g, e12);
-        else launch_gemm<Ops, E12, 4, false, 3, NW>(c, H / 12, c->M / 64, g, e12);
+        if (c->cell_nw == 4) launch_gemm<Ops, E12, 4, false, 3, 4>(c, H / 12, c->M / 64, g, ea);
+        else launch_gemm<Ops, E12, 4, false, 3, NW>(c, H / 12, c->M / 64, g, ea);
         return;
     }
     if (nw == 4) launch_gemm<Ops, E, 2, false, 3, 4>(c, H / 8, c->M / 32, g, ea);
@@ -49,7 +46,7 @@ template <class Ops>
 static void launch_enc_wave_t(lasr_ctx* c, const EncCellRef* cells, int n, int par0, int mt_total) {
     using E = EpiLSTM<Ops, false, false, 8>;
     const int H = c->d.hidden;
-    MultiArgs<E> m{};
+    MultiArgs<LstmArgs> m{};
     unsigned long long* prof = nullptr;
     if (c->cell_prof && c->cp_slots && c->cp_slot_next < lasr_ctx::NCELLSLOT) {
         c->cp_slot_cells[c->cp_slot_next] = (unsigned char)n;
@@ -60,10 +57,10 @@ static void launch_enc_wave_t(lasr_ctx* c, const EncCellRef* cells, int n, int p
         const Cell& L = c->enc[l];
         const void* xsrc = (l == 0) ? c->x0 : c->ybuf[(l - 1) & 1];
         GemmArgs& g = m.g[i];
-        g.A[0] = xsrc; g.a_mt_total[0] = mt_total; g.a_mt_off[0] = t * c->MT; g.KC[0] = L.I / Ops::KCH; g.W[0] = L.WxC;
-        g.A[1] = c->enc_h[par][l]; g.a_mt_total[1] = c->MT; g.a_mt_off[1] = 0; g.KC[1] = H / Ops::KCH; g.W[1] = L.WhC;
+        set_operand(g, 0, xsrc, mt_total, t * c->MT, L.I / Ops::KCH, L.WxC);
+        set_operand(g, 1, c->enc_h[par][l], c->MT, 0, H / Ops::KCH, L.WhC);
         g.M = c->M; g.prof = prof; g.prof_x = prof ? prof + (size_t)PROF_W * lasr_ctx::NCELLSLOT : nullptr; g.prio = c->cell_prio;
-        typename E::Args& ea = m.ea[i];
+        LstmArgs& ea = m.ea[i];
         ea.bias = L.bias; ea.flag = c->T_row_dev; ea.t = t; ea.tile_mask = c->tile_masks.empty() ? ~0ull : c->tile_masks[t];
         ea.c = c->enc_c[l]; ea.h_in = c->enc_h[par][l]; ea.h_out = c->enc_h[par ^ 1][l];
         ea.y = c->ybuf[l & 1]; ea.y_mt_total = mt_total; ea.y_mt_off = t * c->MT;
@@ -72,11 +69,8 @@ static void launch_enc_wave_t(lasr_ctx* c, const EncCellRef* cells, int n, int p
     const int nw = c->cell_nw ? c->cell_nw : (Ops::BF ? 8 : 4);
     if (c->enc_u12) {
         using E12 = EpiLSTMe<Ops, 12>;
-        MultiArgs<E12> m12;
-        static_assert(sizeof(m12) == sizeof(m), "same Args layout");
-        memcpy((void*)&m12, (const void*)&m, sizeof(m12));
-        if (c->cell_nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, 4, false, 3>), dim3(H / 12, c->M / 64, n), dim3(256), 0, c->stream, m12);
-        else hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, NW, false, 3>), dim3(H / 12, c->M / 64, n), dim3(NW * 64), 0, c->stream, m12);
+        if (c->cell_nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, 4, false, 3>), dim3(H / 12, c->M / 64, n), dim3(256), 0, c->stream, m);
+        else hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, NW, false, 3>), dim3(H / 12, c->M / 64, n), dim3(NW * 64), 0, c->stream, m);
         return;
     }
     const dim3 grid(H / 8, c->M / 32, n);
