@@ -92,7 +92,10 @@ struct lasr_ctx {
     // 0 where no such kernel can run (configs[1]); LASR_FE_LDS_PAD overrides (bytes).  Since the same round the wide tilings run on
     // the older matrix instruction (OpsBF16k16: the neighbour that disturbed was v_mfma_f32_16x16x32_bf16 at their density, and only
     // it), after which the probe and the race log are clean WITHOUT the pad as well: the pad is the second line of defence.
-    int fe_lds_pad = 0, logmel_lds_pad = 0;       // (k_fe_mel / the per-chunk k_logmel: 98 304 B minus the kernel's own LDS)
+    int fe_lds_pad = 0;             // (k_fe_mel: 98 304 B minus the kernel's own LDS)
+    // the per-chunk log-mel kernel of the streaming protocols (more than 512 slots, non-standard front-end shapes, irregular clients) runs
+    // beside the decode stream like k_fe_mel: the same CU exclusion against the wide decode tilings (lasr_ctx::fe_lds_pad)
+    int logmel_lds_pad = 0;         // (the per-chunk k_logmel: 98 304 B minus the kernel's own LDS)
     unsigned* enclog = nullptr;     // LASR_DBG_ENCLOG=N: per model step and row, exact checksums (sum of the element bit patterns) of the
     float* pendlog = nullptr;       // LASR_DBG_PENDLOG=1 (with LASR_DBG_ENCLOG): a copy of the pending log-mel frames per logged step
     int enclog_cap = 0, enclog_n = 0;   // encoder's inputs and state behind that step: [N][2 T + 2 L][M], see lasr_debug_enclog
@@ -503,15 +506,5 @@ bool valid_desc(const lasr_model_desc* d) {
     }
     return true;
 }
-
-// k_stack_ln: the reference shape (1280 = 128 mels x 10 frames) has a fully static instantiation
-#define LAUNCH_STACK_LN(grid, block, shmem, stream, args)                                              \
-    do {                                                                                               \
-        if ((args).F == 1280 && (args).n_stack == 10)                                                  \
-            hipLaunchKernelGGL((k_stack_ln<20, 10>), grid, block, shmem, stream, args);                \
-        else                                                                                           \
-            hipLaunchKernelGGL((k_stack_ln<32, 0>), grid, block, shmem, stream, args);                 \
-    } while (0)
-
 
 }  // namespace

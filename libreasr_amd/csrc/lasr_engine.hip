@@ -11,7 +11,12 @@ static int cont_pump(lasr_ctx* c, int G);
 static int pump_start(lasr_ctx* c);
 static void pump_kick(lasr_ctx* c);
 static int flush_lazy(lasr_ctx* c);       // (deferred ring append of lasr_push_submit)
+struct PushSrc;
+static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fused, bool* fused_done);
+static int push_submit_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, int flags, long long* ticket, const float* const* rows);
+static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStream_t sa = nullptr, hipStream_t sb = nullptr);
 #include "lasr_cmd.hip.h"
+#include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
 #include "lasr_weights.hip.h"
 
@@ -100,8 +105,6 @@ void lasr_destroy(lasr_ctx* c) {
 
 const char* lasr_last_error(const lasr_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 
-static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStream_t sa = nullptr, hipStream_t sb = nullptr);
-
 static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
     roctx_init();
     const lasr_model_desc& d = c->d;
@@ -157,10 +160,6 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         //  128 streams, greedy / beam 8: 46.8 / 14.6 k against 45.9 / 14.4 k as a wavefront, profiles/r04/r04_cell_tiling_d.txt)
         if (c->enc_u12) c->enc_wave = 0;
         if (getenv("LASR_ENC_WAVE")) c->enc_wave = atoi(getenv("LASR_ENC_WAVE"));
-        // decode-stream GEMMs (predictor cells, PPJ, logits): 8 waves per workgroup with either operand type.  (Rounds 2-5 ran them on
-        // 4 waves with f32 operands: +5 % whole job when the decode loop had slack; with the loop the binding stream -- 18 steps in
-        // flight, 92 % busy -- 8 waves win: 53.5-53.6 -> 54.2-54.6 k timed, 57.3-57.5 -> 57.6-58.3 k sustained, same box, 4 runs each:
-        // profiles/r06/r06_experiments.txt T)
         if (getenv("LASR_DBG_TIMING")) {
             RC(dalloc0(c, &c->dbg, (size_t)5 * 4096 * 16));
         }
@@ -315,8 +314,6 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
     RC(dalloc0(c, &c->pub_arrivals, 4));
     RC(dalloc0(c, &c->T_row_fix, M));
     RC(dalloc0(c, &c->T_row_main, M));
-    // measured (profiles/r03/r03_experiments.txt I): host time per model step 66 -> 45 us, but the replay starts its first cell ~6 us
-    // later than a plain launch does: f32 -2 % (52.8 against 54.0 k audio-s/s), bf16 +0.5 %  =>  on for bf16, off for f32
     {   // see lasr_ctx::fe_lds_pad.  The kernels' own (static) LDS is asked of the runtime, not assumed
         hipFuncAttributes fa{}, la_{};
         HIPCHK(c, hipFuncGetAttributes(&fa, (const void*)k_fe_mel<10>));
@@ -328,7 +325,10 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         c->logmel_lds_pad = c->fe_lds_pad ? std::max(0, excl - (int)la_.sharedSizeBytes) : 0;
         HIPCHK(c, hipFuncSetAttribute((const void*)k_fe_mel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cu - (int)fa.sharedSizeBytes));
         HIPCHK(c, hipFuncSetAttribute((const void*)k_logmel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cu - (int)la_.sharedSizeBytes));
+        HIPCHK(c, hipFuncSetAttribute((const void*)k_ln_tile, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
     }
+    // measured (profiles/r03/r03_experiments.txt I): host time per model step 66 -> 45 us, but the replay starts its first cell ~6 us
+    // later than a plain launch does: f32 -2 % (52.8 against 54.0 k audio-s/s), bf16 +0.5 %  =>  on for bf16, off for f32
     c->main_graph = c->bf != 0;
     if (getenv("LASR_MAIN_GRAPH")) c->main_graph = atoi(getenv("LASR_MAIN_GRAPH")) != 0;
     c->T_row_dev = c->zero_rows;
@@ -583,28 +583,9 @@ int lasr_stream_close(lasr_ctx* c, int slot) {
 
 // ---------------------------------------------------------------------------- streaming
 
-static void fill_mel_args(lasr_ctx* c, MelArgs& m) {
-    const lasr_model_desc& d = c->d;
-    m.window = c->window; m.tw512 = c->tw512; m.tw1024 = c->tw1024; m.fb_start = c->fb_start; m.fb_off = c->fb_off;
-    m.fb_w = c->fb_w; m.n_mels = d.n_mels; m.hop = d.hop;
-    m.win_off = (d.n_fft - d.win) / 2; m.win_len = d.win; m.fb_nnz = c->fb_nnz;
-}
-// window geometry of the streaming front-end (api-server.py:95-102 + TransformTime + StreamPostprocess): first frame picked
-static int stream_frame0(lasr_ctx* c, int* nf_out) {
-    const lasr_model_desc& d = c->d;
-    const long long N = (long long)d.n_window * d.chunk;
-    const int T = 1 + (int)(N / d.hop);
-    const int a0 = T / 3 + 1;
-    if (nf_out) *nf_out = std::min(d.n_stack, T - a0);
-    return a0;
-}
-
 // Fused front-end, irregular clients: a slot that is about to be pushed again although it still has a pending frame whose
 // window the ring would lose (more than one chunk pushed per lasr_step_* call) gets that frame computed NOW into `pend`
 // (the per-chunk log-mel kernel, window selected by its age); the step's k_fe_mel launch then skips it (age 15).
-// the per-chunk log-mel kernel of the streaming protocols (more than 512 slots, non-standard front-end shapes, irregular clients) runs
-// beside the decode stream like k_fe_mel: the same CU exclusion against the wide decode tilings (lasr_ctx::fe_lds_pad)
-static int logmel_lds_pad(lasr_ctx* c) { return c->logmel_lds_pad; }
 static int materialize_pending(lasr_ctx* c, const int* slots, int n) {
     const lasr_model_desc& d = c->d;
     const int slack = c->ring_chunks - d.n_window;
@@ -623,12 +604,8 @@ static int materialize_pending(lasr_ctx* c, const int* slots, int n) {
         }
         if (!any) continue;
         RC(flush_lazy(c));                                       // (the kernel below reads the ring)
-        fill_mel_args(c, m);
-        m.pcm = c->win; m.N = (long long)d.n_window * d.chunk; m.stream = 1; m.ring_head = c->ring_pos; m.chunk = d.chunk;
-        m.n_window = d.n_window; m.ring_chunks = c->ring_chunks; m.frame0 = stream_frame0(c, nullptr);
-        m.frames_per_row = d.n_stack; m.out = c->pend; m.out_frames = d.n_buffer * d.n_stack;
         m.by_value = 1; m.trow_out = nullptr;
-        hipLaunchKernelGGL(k_logmel, dim3((d.n_stack + 3) / 4, c->M), dim3(256), logmel_lds_pad(c), c->stream, m);
+        launch_logmel_ring(c, m);
     }
     return LASR_OK;
 }
@@ -854,6 +831,38 @@ int lasr_push_consumed(lasr_ctx* c, long long ticket) {
     return fail(c, LASR_EHIP, "hipEventQuery failed: %s", hipGetErrorString(e));
 }
 
+// ---- step plumbing shared by the entry points below
+// a host source is copied (stream-ordered) into the growable device buffer *buf; a device source is used where it is
+static int stage_to_device(lasr_ctx* c, const float* p, size_t n, float** buf, size_t* have, const float** src) {
+    *src = p;
+    if (is_device_ptr(p)) return LASR_OK;
+    RC(ensure_buf(c, buf, have, n));
+    HIPCHK(c, hipMemcpyAsync(*buf, p, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    *src = *buf;
+    return LASR_OK;
+}
+// a frame of slot s has been collected; Buffer.encodes: emit when n_buffer collected -- the slot then joins the model step
+static void frame_collected(lasr_ctx* c, int s, std::vector<int>& model_rows) {
+    if (++c->n_pend[s] != c->d.n_buffer) return;
+    c->n_pend[s] = 0;
+    c->hc.T_row[s] = c->d.n_buffer;
+    model_rows.push_back(s);
+}
+static void encode_step(lasr_ctx* c, int T) {
+    rec(c, 1);
+    run_encoder(c, T);
+    rec(c, 2);
+}
+// tail of every synchronous step: decode the T encoded frames of `rows`, wait for the ctx stream, collect the statistics
+static int decode_and_collect(lasr_ctx* c, int T, int max_iters, bool offline, const std::vector<int>& rows) {
+    RC(run_decode(c, T, max_iters, offline, rows));
+    rec(c, 3);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    collect_stats(c, T);
+    return LASR_OK;
+}
+
 // front-end of one client chunk for the listed slots and, for the slots whose frame buffer filled up,
 // LayerNorm + encoder + encoder half of the joint -- all enqueued on c->stream, nothing synchronises
 // fused (lasr_push_submit): the listed slots' newest chunk is still in the caller's buffer `fused->src` (row i of it belongs to
@@ -862,12 +871,10 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
                                     const PushSrc* fused = nullptr, bool* fused_done = nullptr) {
     RoctxRange roctx_range_("lasr frontend+encoder");
     const lasr_model_desc& d = c->d;
-    // window geometry (api-server.py:95-102 + TransformTime + StreamPostprocess)
-    const long long N = (long long)d.n_window * d.chunk;
     int nf = 0;
-    const int a0 = stream_frame0(c, &nf);
-    if (nf < d.n_stack) return fail(c, LASR_EINVAL, "chunk of %d samples is too short: window yields %d < n_stack frames", d.chunk, nf);
-    if (N <= d.n_fft / 2) return fail(c, LASR_EINVAL, "window shorter than the reflect padding");
+    const int fault = stream_window_fault(c, &nf);
+    if (fault == 1) return fail(c, LASR_EINVAL, "chunk of %d samples is too short: window yields %d < n_stack frames", d.chunk, nf);
+    if (fault == 2) return fail(c, LASR_EINVAL, "window shorter than the reflect padding");
     RC(cmd_begin(c));
     model_rows.clear();
     Tm = d.n_buffer;
@@ -879,11 +886,7 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
             if (c->n_chunks[s] < d.n_window) continue;          // window not full: the servicer does not call the pipeline
             const size_t q = (size_t)s * d.n_buffer + c->n_pend[s];
             c->pend_serial[q] = c->n_chunks[s]; c->pend_mat[q] = 0;
-            if (++c->n_pend[s] == d.n_buffer) {                  // Buffer.encodes: emit when n_buffer collected
-                c->n_pend[s] = 0;
-                c->hc.T_row[s] = d.n_buffer;
-                model_rows.push_back(s);
-            }
+            frame_collected(c, s, model_rows);
         }
         rec(c, 0);
         if (model_rows.empty()) return LASR_OK;
@@ -904,16 +907,12 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
         {
             // log-mel halves (+ the ring append of the newest chunk when fused) on 2 x n_buffer x rows workgroups, then stack + LayerNorm
             FeMelArgs m{};
-            m.window = c->window; m.tw512 = c->tw512; m.tw1024 = c->tw1024; m.fb_start = c->fb_start; m.fb_off = c->fb_off; m.fb_w = c->fb_w;
-            m.n_mels = d.n_mels; m.hop = d.hop; m.fb_nnz = c->fb_nnz; m.win_off = (d.n_fft - d.win) / 2; m.win_len = d.win;
-            m.pcm = c->win; m.ring_pos = c->ring_pos; m.chunk = d.chunk; m.n_window = d.n_window; m.ring_chunks = c->ring_chunks; m.frame0 = a0;
-            m.pend = c->pend; m.pend_frames = d.n_buffer * d.n_stack;
+            fill_fe_mel_args(c, m, c->pend);
             int* trow_home = (c->pe == c->pe_ring) ? c->T_row_main : nullptr;      // pipelined: one fixed buffer (see commit_T_rows)
             m.trow_out = trow_home ? trow_home : c->dc.T_row; m.enc_frames = enc_frames; m.enc_base = enc_base;
             m.src = fused ? fused->src : nullptr;
             const bool with_lazy = fused && c->lazy.on;          // (push_submit_impl: the deferred chunk belongs to exactly `slots`)
             m.src2 = with_lazy ? c->lazy.src : nullptr;
-            for (int r = 0; r < 512; ++r) { m.idx[r] = -1; m.tp_pk[r] = 0; m.age_pk[r] = 0; }
             for (int r = 0; r < c->M; ++r) m.tp_pk[r] = (unsigned char)(c->h_ring_pos[r] << 4);
             if (fused)
                 for (int i = 0; i < n; ++i) {
@@ -927,40 +926,17 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
                 for (int j = 0; j < d.n_buffer; ++j) { const unsigned a8 = age_v[(size_t)j * c->M + s]; pk |= (a8 == 255 ? 15u : a8) << (4 * j); }
                 m.age_pk[s] = (unsigned short)pk;
             }
-            hipStream_t fe_st = c->stream;
             if (fused) {
                 RC(wait_copied(c, *fused));
                 if (with_lazy && c->lazy.dma && !fused->dma) { PushSrc lz; lz.ev_i = c->lazy.ev_i; lz.dma = true; RC(wait_copied(c, lz)); }
             }
-            // c->fe_lds_pad bytes of unused dynamic LDS: the workgroup then shares its CU with no workgroup of the wide decode tilings
-            // (see lasr_ctx::fe_lds_pad)
-            hipLaunchKernelGGL((k_fe_mel<10>), dim3(2 * d.n_buffer, c->M), dim3(320), c->fe_lds_pad, fe_st, m);
+            launch_fe_mel(c, m);
             if (fused_done) *fused_done = fused != nullptr;
             if (with_lazy) { c->lazy_taken++; RC(lazy_consumed(c)); }
             RC(commit_T_rows(c, Tm, /*fixed_copy=*/c->pe != c->pe_ring, trow_home));    // the continuous loop reads its own frame counters
-            StackLnArgs a{};
-            a.src = c->pend; a.mode = 0; a.src_frames = d.n_buffer * d.n_stack; a.frame_step = d.n_stack; a.row_off = nullptr;
-            a.T_row = c->T_row_dev; a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels;
-            a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT; a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = Tm;
-            if (d.feat == 1280 && d.n_stack == 10 && d.n_mels == 128) {
-                LnTileArgs t{};
-                t.pend = c->pend; t.pend_frames = d.n_buffer * d.n_stack; t.T_row = c->T_row_dev; t.ln_w = c->ln_w; t.ln_b = c->ln_b;
-                t.x0 = c->x0; t.MT = c->MT; t.mt_total = c->Tcap * c->MT; t.bf = c->bf;
-                static bool attr = false;
-                if (!attr) { (void)hipFuncSetAttribute((const void*)k_ln_tile, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024); attr = true; }
-                // store phase of the tile kernel on 4 z-slices (8 -> 32 workgroups; bit-identical): f32 52.5-52.7 -> 52.6-53.3 k, bf16
-                // 92.8 -> 95.4 k (profiles/r04/r04_lnz_ab.txt)
-                constexpr int ln_z = 4;
-                // (with wide decode tilings around: 98 304 B instead of the 82 176 the tile needs -- the same CU exclusion as the log-mel
-                //  launch's; this kernel reads its tile back with wide LDS reads as well and has never been seen wrong)
-                hipLaunchKernelGGL(k_ln_tile, dim3(c->MT, Tm, ln_z), dim3(1024), c->fe_lds_pad ? 98304 : 16 * 1284 * 4, fe_st, t);
-            } else {
-                LAUNCH_STACK_LN( dim3((Tm + 3) / 4, c->M), dim3(256), 0, fe_st, a);
-            }
+            launch_ln_tile(c, Tm);
         }
-        rec(c, 1);
-        run_encoder(c, Tm);
-        rec(c, 2);
+        encode_step(c, Tm);
         return LASR_OK;
     }
     bool any_feat = false;
@@ -970,11 +946,7 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
         if (c->n_chunks[s] < d.n_window) continue;          // window not full: the servicer does not call the pipeline
         c->hc.feat_sel[s] = c->n_pend[s] * d.n_stack;
         any_feat = true;
-        if (++c->n_pend[s] == d.n_buffer) {                  // Buffer.encodes: emit when n_buffer collected
-            c->n_pend[s] = 0;
-            c->hc.T_row[s] = d.n_buffer;
-            model_rows.push_back(s);
-        }
+        frame_collected(c, s, model_rows);
     }
     // <= 512 rows: the command (frame slot + frames of this model step per row) rides in the log-mel launch's
     // arguments; otherwise it goes through the command ring (one host->device copy)
@@ -983,31 +955,19 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
     rec(c, 0);
     if (any_feat) {
         MelArgs m{};
-        fill_mel_args(c, m);
-        m.pcm = c->win; m.N = N; m.stream = 1;
-        m.ring_head = c->ring_pos; m.chunk = d.chunk; m.n_window = d.n_window; m.ring_chunks = c->ring_chunks; m.row_sel = c->dc.feat_sel; m.frame0 = a0;
-        m.frames_per_row = d.n_stack; m.out = c->pend; m.out_frames = d.n_buffer * d.n_stack;
-        m.row_N = nullptr; m.row_src_off = nullptr; m.row_frames = nullptr;
+        m.row_sel = c->dc.feat_sel;
         if (by_value) {
             m.by_value = 1;
             m.trow_out = model_rows.empty() ? nullptr : c->dc.T_row;
             for (int r = 0; r < c->M; ++r) { m.sel_v[r] = (short)c->hc.feat_sel[r]; m.trow_v[r] = (unsigned char)c->hc.T_row[r]; }
         }
-        hipLaunchKernelGGL(k_logmel, dim3((d.n_stack + 3) / 4, c->M), dim3(256), logmel_lds_pad(c), c->stream, m);
+        launch_logmel_ring(c, m);
     }
     if (model_rows.empty()) return LASR_OK;
     RC(ensure_T(c, Tm));
     RC(commit_T_rows(c, Tm, /*fixed_copy=*/c->pe != c->pe_ring));    // the continuous loop reads its own frame counters
-    {
-        StackLnArgs a{};
-        a.src = c->pend; a.mode = 0; a.src_frames = d.n_buffer * d.n_stack; a.frame_step = d.n_stack; a.row_off = nullptr;
-        a.T_row = c->T_row_dev; a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels;
-        a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT; a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = Tm;
-        LAUNCH_STACK_LN( dim3((Tm + 3) / 4, c->M), dim3(256), 0, c->stream, a);
-    }
-    rec(c, 1);
-    run_encoder(c, Tm);
-    rec(c, 2);
+    stack_ln_logmel(c, c->pend, d.n_buffer * d.n_stack, d.n_stack, c->T_row_dev, Tm);
+    encode_step(c, Tm);
     return LASR_OK;
 }
 
@@ -1026,11 +986,7 @@ int lasr_step_stream(lasr_ctx* c, const int* slots, int n, int* n_ran) {
         HIPCHK(c, hipGetLastError());
         return LASR_OK;
     }
-    RC(run_decode(c, Tm, c->d.max_iters_stream, false, model_rows));
-    rec(c, 3);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    collect_stats(c, Tm);
+    RC(decode_and_collect(c, Tm, c->d.max_iters_stream, false, model_rows));
     if (n_ran) *n_ran = (int)model_rows.size();
     return LASR_OK;
 }
@@ -1048,7 +1004,6 @@ int lasr_step_stream(lasr_ctx* c, const int* slots, int n, int* n_ran) {
 // encoder, so decoding resumes without the host).
 // Tokens are attributed to the step whose frames produced them: per-step results are identical to
 // lasr_step_stream.
-static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fused, bool* fused_done);
 int lasr_step_submit(lasr_ctx* c, const int* slots, int n) {
     if (!c) return LASR_EINVAL;
     RC(check_slots(c, slots, n, true));
@@ -1058,7 +1013,6 @@ int lasr_step_submit(lasr_ctx* c, const int* slots, int n) {
 
 // lasr_push_pcm_ex + lasr_step_submit in one call: when the chunk completes a model step, the front-end launch reads the newest
 // chunk straight from the source buffer and appends it to the PCM ring itself (one launch less per model step).
-static int push_submit_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, int flags, long long* ticket, const float* const* rows);
 int lasr_push_submit(lasr_ctx* c, const int* slots, int n, const float* pcm, int flags, long long* ticket) {
     if (!c) return LASR_EINVAL;
     return push_submit_impl(c, slots, n, pcm, flags, ticket, nullptr);
@@ -1086,12 +1040,8 @@ static int push_submit_impl(lasr_ctx* c, const int* slots, int n, const float* p
     if ((int)c->pending.size() + 1 > lasr_max_inflight(c))
         return fail(c, LASR_ESTATE, "%d steps already in flight (limit %d): call lasr_step_wait (nothing was pushed)", (int)c->pending.size(), lasr_max_inflight(c));
     if (c->W > 1 && c->M > 512) return fail(c, LASR_ESTATE, "the pipelined protocol with beam > 1 takes up to 512 stream slots (nothing was pushed)");
-    {
-        int nf = 0;
-        (void)stream_frame0(c, &nf);
-        if (nf < c->d.n_stack || (long long)c->d.n_window * c->d.chunk <= c->d.n_fft / 2)
-            return fail(c, LASR_EINVAL, "chunk of %d samples is too short for the streaming window (nothing was pushed)", c->d.chunk);
-    }
+    if (stream_window_fault(c))
+        return fail(c, LASR_EINVAL, "chunk of %d samples is too short for the streaming window (nothing was pushed)", c->d.chunk);
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->pending.empty()) RC(cont_pump(c, c->kick_n));
     PushSrc ps;
@@ -1130,11 +1080,9 @@ static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fuse
     if (c->W > 1 && c->M > 512) return fail(c, LASR_ESTATE, "the pipelined protocol with beam > 1 takes up to 512 stream slots");
     {   // in-flight limit: the event / T_row rings (NFLY) and the per-row rings the decode loop runs through --
         // encoder frames not yet decoded (pe ring), tokens not yet collected (token ring), step boundary marks
-        const int inflight = (int)c->pending.size() + 1, Tm = c->d.n_buffer;
-        if (inflight > lasr_ctx::NFLY - 1 || inflight > lasr_ctx::ENDSLOTS || inflight * Tm > lasr_ctx::RING ||
-            inflight * Tm * c->d.max_iters_stream > lasr_ctx::TOKRING)
+        if ((int)c->pending.size() + 1 > lasr_max_inflight(c))
             return fail(c, LASR_ESTATE, "%d steps already in flight (limit %d for n_buffer %d, max_iters_stream %d): call lasr_step_wait",
-                        (int)c->pending.size(), lasr_max_inflight(c), Tm, c->d.max_iters_stream);
+                        (int)c->pending.size(), lasr_max_inflight(c), c->d.n_buffer, c->d.max_iters_stream);
     }
     HIPCHK(c, hipSetDevice(c->device));
     // keep the decode stream busy while the host enqueues (and the GPU runs) this chunk's encoder (a no-op with the pump thread)
@@ -1184,6 +1132,47 @@ static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fuse
     return LASR_OK;
 }
 
+// ---- the pinned marks and tokens of the continuous greedy loop (k_select stores them, see create_impl): host views
+// token count of row r at the end of the model step of P it takes part in = end of that step's tokens in the row's ring
+static long long step_end_mark(const lasr_ctx* c, const lasr_ctx::PendingStep& P, int r) {
+    const int* h_end = c->cont_host + 16 + (size_t)lasr_ctx::NFLY * c->M;
+    const int j = P.target[r] / P.Tm - 1;
+    return h_end[(size_t)r * lasr_ctx::ENDSLOTS + (j % lasr_ctx::ENDSLOTS)];
+}
+// token q (counted since the row was opened) of row r
+static int32_t ring_token(const lasr_ctx* c, int r, long long q) {
+    const int* h_ring = c->cont_host + 16 + (size_t)(lasr_ctx::NFLY + lasr_ctx::ENDSLOTS) * c->M;
+    return h_ring[(size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)];
+}
+
+// The submitted, uncollected steps of one slot, oldest first (c->mu held, cursors polled): *n_inflight counts them, *n_decoded the
+// leading ones the decode loop has finished for the slot; those behind the `skip` oldest hand counts[k] tokens each to `tokens`.
+// `who` names the caller in the LASR_EFULL text.
+static int peek_walk(lasr_ctx* c, const char* who, int slot, int skip, int32_t* tokens, int cap, int32_t* counts, int cap_steps,
+                     int* n_decoded, int* n_inflight) {
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    long long from = c->h_fetched[slot];
+    int used = 0, kept = 0;
+    bool open_run = true;
+    for (const auto& P : c->pending) {
+        if (P.target[slot] == 0) continue;                       // the slot is not part of this step
+        const int k = (*n_inflight)++;
+        if (!open_run || c->h_cur_seen[slot] < P.target[slot]) { open_run = false; continue; }
+        const long long end = step_end_mark(c, P, slot);
+        if (k >= skip) {
+            const int cnt = (int)(end - from);
+            if (kept >= cap_steps || used + cnt > cap) return fail(c, LASR_EFULL, "%s: buffers too small", who);
+            if (counts) counts[kept] = cnt;
+            if (tokens)
+                for (long long q = from; q < end; ++q) tokens[used++] = ring_token(c, slot, q);
+            kept++;
+        }
+        from = end;
+        (*n_decoded)++;
+    }
+    return LASR_OK;
+}
+
 // Non-consuming look at the submitted, uncollected model steps of one slot (greedy decode): how many there are, how many of
 // them (oldest first) the decode loop has finished for this slot, and the tokens of those -- counts[k] tokens for step k,
 // concatenated in `tokens`.  lasr_step_wait / lasr_fetch hand the same tokens out later, in step order, as if nobody had looked.
@@ -1194,30 +1183,9 @@ int lasr_peek_slot(lasr_ctx* c, int slot, int32_t* tokens, int cap, int32_t* cou
     *n_decoded = 0; *n_inflight = 0;
     if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
     if (c->W > 1) return fail(c, LASR_ESTATE, "lasr_peek_slot serves greedy decode (beam = 1)");
-    const int M = c->M;
-    const int* h_end = c->cont_host + 16 + (size_t)lasr_ctx::NFLY * M;
-    const int* h_ring = h_end + (size_t)M * lasr_ctx::ENDSLOTS;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->pump_on) cont_poll(c);
-    long long from = c->h_fetched[slot];
-    int used = 0;
-    bool open_run = true;
-    for (const auto& P : c->pending) {
-        if (std::find(P.rows.begin(), P.rows.end(), slot) == P.rows.end()) continue;
-        const int k = (*n_inflight)++;
-        if (!open_run || c->h_cur_seen[slot] < P.target[slot]) { open_run = false; continue; }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        const int j = P.target[slot] / P.Tm - 1;
-        const long long end = h_end[(size_t)slot * lasr_ctx::ENDSLOTS + (j % lasr_ctx::ENDSLOTS)];
-        const int n = (int)(end - from);
-        if (k >= cap_steps || used + n > cap) return fail(c, LASR_EFULL, "lasr_peek_slot: buffers too small");
-        if (counts) counts[k] = n;
-        for (long long q = from; q < end; ++q)
-            if (tokens) tokens[used++] = h_ring[(size_t)slot * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)];
-        from = end;
-        (*n_decoded)++;
-    }
-    return LASR_OK;
+    return peek_walk(c, "lasr_peek_slot", slot, 0, tokens, cap, counts, cap_steps, n_decoded, n_inflight);
 }
 
 // lasr_peek_slot for n slots in one call: skip[i] oldest steps of slots[i] are of no interest (the caller has seen them);
@@ -1227,37 +1195,14 @@ int lasr_peek_many(lasr_ctx* c, const int* slots, int n, const int* skip, int32_
                    int* n_decoded, int* n_inflight) {
     if (!c || !slots || !n_decoded || !n_inflight || n < 0) return LASR_EINVAL;
     if (c->W > 1) return fail(c, LASR_ESTATE, "lasr_peek_many serves greedy decode (beam = 1)");
-    const int M = c->M;
-    const int* h_end = c->cont_host + 16 + (size_t)lasr_ctx::NFLY * M;
-    const int* h_ring = h_end + (size_t)M * lasr_ctx::ENDSLOTS;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->pump_on) cont_poll(c);
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
         n_decoded[i] = 0; n_inflight[i] = 0;
         if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
-        long long from = c->h_fetched[slot];
-        int used = 0, kept = 0;
-        bool open_run = true;
-        const int sk = skip ? skip[i] : 0;
-        for (const auto& P : c->pending) {
-            if (P.target[slot] == 0) continue;                       // the slot is not part of this step
-            const int k = n_inflight[i]++;
-            if (!open_run || c->h_cur_seen[slot] < P.target[slot]) { open_run = false; continue; }
-            const int j = P.target[slot] / P.Tm - 1;
-            const long long end = h_end[(size_t)slot * lasr_ctx::ENDSLOTS + (j % lasr_ctx::ENDSLOTS)];
-            if (k >= sk) {
-                const int cnt = (int)(end - from);
-                if (kept >= cap_steps || used + cnt > cap) return fail(c, LASR_EFULL, "lasr_peek_many: buffers too small");
-                if (counts) counts[(size_t)i * cap_steps + kept] = cnt;
-                if (tokens)
-                    for (long long q = from; q < end; ++q) tokens[(size_t)i * cap + used++] = h_ring[(size_t)slot * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)];
-                kept++;
-            }
-            from = end;
-            n_decoded[i]++;
-        }
+        RC(peek_walk(c, "lasr_peek_many", slot, skip ? skip[i] : 0, tokens ? tokens + (size_t)i * cap : nullptr, cap,
+                     counts ? counts + (size_t)i * cap_steps : nullptr, cap_steps, &n_decoded[i], &n_inflight[i]));
     }
     return LASR_OK;
 }
@@ -1692,10 +1637,7 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
         if (c->pending.empty()) return LASR_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const int M = c->M;
     int* flag = c->cont_host;
-    int* h_end = c->cont_host + 16 + (size_t)lasr_ctx::NFLY * M;
-    int* h_ring = h_end + (size_t)M * lasr_ctx::ENDSLOTS;
     if (c->pump_on) {
         // the pump thread launches the groups and consumes their flags: wait for its progress counter
         for (unsigned long long guard = 0;; ++guard) {
@@ -1748,10 +1690,8 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
         }
     } else
     for (int r : P.rows) {
-        const int j = P.target[r] / P.Tm - 1;
-        const long long end = h_end[(size_t)r * lasr_ctx::ENDSLOTS + (j % lasr_ctx::ENDSLOTS)];
-        for (long long q = c->h_fetched[r]; q < end; ++q)
-            c->queue[r].push_back(h_ring[(size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)]);
+        const long long end = step_end_mark(c, P, r);
+        for (long long q = c->h_fetched[r]; q < end; ++q) c->queue[r].push_back(ring_token(c, r, q));
         c->h_fetched[r] = end;
     }
     c->stats.frames = P.Tm;
@@ -1765,22 +1705,6 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
 }
 
 // ---------------------------------------------------------------------------- offline
-static int transcribe_common(lasr_ctx* c, const int* slots, int n, int T_max) {
-    // cmd block (T_row, what) already filled + committed by the caller; x0 holds the features
-    const lasr_model_desc& d = c->d;
-    std::vector<int> rows(slots, slots + n);
-    RC(commit_T_rows(c, T_max));
-    rec(c, 1);
-    run_encoder(c, T_max);
-    rec(c, 2);
-    RC(run_decode(c, T_max, d.max_iters_offline, true, rows));
-    rec(c, 3);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    collect_stats(c, T_max);
-    return LASR_OK;
-}
-
 int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples) {
     RoctxRange roctx_range_("lasr_transcribe");
     if (!c) return LASR_EINVAL;
@@ -1802,12 +1726,8 @@ int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, 
         total += n_samples[i];
     }
     RC(ensure_T(c, T_max));
-    const float* src = pcm;
-    if (!is_device_ptr(pcm)) {
-        RC(ensure_buf(c, &c->stage_pcm, &c->stage_pcm_floats, (size_t)total));
-        HIPCHK(c, hipMemcpyAsync(c->stage_pcm, pcm, sizeof(float) * (size_t)total, hipMemcpyHostToDevice, c->stream));
-        src = c->stage_pcm;
-    }
+    const float* src = nullptr;
+    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
     RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
     RC(cmd_begin(c));
     long long off = 0;
@@ -1823,20 +1743,11 @@ int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, 
     RC(cmd_commit(c));
     RC(apply_reset(c, true));
     rec(c, 0);
-    MelArgs m{};
-    m.window = c->window; m.tw512 = c->tw512; m.tw1024 = c->tw1024; m.fb_start = c->fb_start; m.fb_off = c->fb_off;
-    m.fb_w = c->fb_w; m.n_mels = d.n_mels; m.hop = d.hop; m.pcm = src; m.N = 0; m.stream = 0;
-    m.ring_head = nullptr; m.chunk = d.chunk; m.n_window = d.n_window; m.row_sel = nullptr; m.frame0 = 0;
-    m.frames_per_row = Tmel_max; m.out = c->lm_buf; m.out_frames = Tmel_max;
-    m.row_N = c->dc.row_N; m.row_src_off = c->dc.row_src_off; m.row_frames = c->dc.row_frames;
-    m.win_off = (d.n_fft - d.win) / 2; m.win_len = d.win; m.fb_nnz = c->fb_nnz;
-    hipLaunchKernelGGL(k_logmel, dim3((Tmel_max + 3) / 4, c->M), dim3(256), 0, c->stream, m);
-    StackLnArgs a{};
-    a.src = c->lm_buf; a.mode = 0; a.src_frames = Tmel_max; a.frame_step = d.stride; a.row_off = nullptr;
-    a.T_row = c->dc.T_row; a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels;
-    a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT; a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = T_max;
-    LAUNCH_STACK_LN( dim3((T_max + 3) / 4, c->M), dim3(256), 0, c->stream, a);
-    return transcribe_common(c, slots, n, T_max);
+    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
+    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return decode_and_collect(c, T_max, d.max_iters_offline, true, std::vector<int>(slots, slots + n));
 }
 
 int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames) {
@@ -1854,12 +1765,8 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
         T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
     }
     RC(ensure_T(c, T_max));
-    const float* src = feats;
-    if (!is_device_ptr(feats)) {
-        RC(ensure_buf(c, &c->feat_stage, &c->feat_stage_floats, (size_t)total * d.feat));
-        HIPCHK(c, hipMemcpyAsync(c->feat_stage, feats, sizeof(float) * (size_t)total * d.feat, hipMemcpyHostToDevice, c->stream));
-        src = c->feat_stage;
-    }
+    const float* src = nullptr;
+    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
     RC(cmd_begin(c));
     long long off = 0;
     for (int i = 0; i < n; ++i) {
@@ -1873,12 +1780,10 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
     RC(cmd_commit(c));
     RC(apply_reset(c, true));
     rec(c, 0);
-    StackLnArgs a{};
-    a.src = src; a.mode = 1; a.src_frames = 0; a.frame_step = 0; a.row_off = c->dc.row_feat_off;
-    a.T_row = c->dc.T_row; a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels;
-    a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT; a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = T_max;
-    LAUNCH_STACK_LN( dim3((T_max + 3) / 4, c->M), dim3(256), 0, c->stream, a);
-    return transcribe_common(c, slots, n, T_max);
+    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return decode_and_collect(c, T_max, d.max_iters_offline, true, std::vector<int>(slots, slots + n));
 }
 
 // Transducer.transcribe_stream on feature chunks (models.py:506-575): carried encoder / predictor
@@ -1893,32 +1798,17 @@ int lasr_step_feats(lasr_ctx* c, const int* slots, int n, const float* feats, in
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
     RC(ensure_T(c, T));
-    const float* src = feats;
-    if (!is_device_ptr(feats)) {
-        RC(ensure_buf(c, &c->feat_stage, &c->feat_stage_floats, (size_t)n * T * d.feat));
-        HIPCHK(c, hipMemcpyAsync(c->feat_stage, feats, sizeof(float) * (size_t)n * T * d.feat, hipMemcpyHostToDevice, c->stream));
-        src = c->feat_stage;
-    }
+    const float* src = nullptr;
+    RC(stage_to_device(c, feats, (size_t)n * T * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
     RC(cmd_begin(c));
     std::vector<int> rows(slots, slots + n);
     for (int i = 0; i < n; ++i) { c->hc.T_row[slots[i]] = T; c->hc.row_feat_off[slots[i]] = (long long)i * T; }
     RC(cmd_commit(c));
     RC(commit_T_rows(c, T));
     rec(c, 0);
-    StackLnArgs a{};
-    a.src = src; a.mode = 1; a.row_off = c->dc.row_feat_off; a.T_row = c->T_row_dev; a.ln_w = c->ln_w; a.ln_b = c->ln_b;
-    a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels; a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT;
-    a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = T;
-    LAUNCH_STACK_LN( dim3((T + 3) / 4, c->M), dim3(256), 0, c->stream, a);
-    rec(c, 1);
-    run_encoder(c, T);
-    rec(c, 2);
-    RC(run_decode(c, T, d.max_iters_stream, false, rows));
-    rec(c, 3);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    collect_stats(c, T);
-    return LASR_OK;
+    stack_ln_feats(c, src, c->dc.row_feat_off, c->T_row_dev, T);
+    encode_step(c, T);
+    return decode_and_collect(c, T, d.max_iters_stream, false, rows);
 }
 
 int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, double* neg_logp, double* align) {
@@ -1960,14 +1850,7 @@ int lasr_logmel(lasr_ctx* c, const float* pcm, int B, int64_t N, float* logmel) 
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
     const int T = 1 + (int)(N / d.hop);
-    MelArgs m{};
-    m.window = c->window; m.tw512 = c->tw512; m.tw1024 = c->tw1024; m.fb_start = c->fb_start; m.fb_off = c->fb_off;
-    m.fb_w = c->fb_w; m.n_mels = d.n_mels; m.hop = d.hop; m.pcm = pcm; m.N = N; m.stream = 0;
-    m.ring_head = nullptr; m.chunk = d.chunk; m.n_window = d.n_window; m.row_sel = nullptr; m.frame0 = 0;
-    m.frames_per_row = T; m.out = logmel; m.out_frames = T;
-    m.row_N = nullptr; m.row_src_off = nullptr; m.row_frames = nullptr;
-    m.win_off = (d.n_fft - d.win) / 2; m.win_len = d.win; m.fb_nnz = c->fb_nnz;
-    hipLaunchKernelGGL(k_logmel, dim3((T + 3) / 4, B), dim3(256), 0, c->stream, m);
+    launch_logmel_offline(c, pcm, N, B, T, logmel);
     HIPCHK(c, hipGetLastError());
     return LASR_OK;
 }
@@ -1996,11 +1879,7 @@ int lasr_encoder(lasr_ctx* c, const float* feats, int B, int Tp, float* out, flo
     RC(cmd_commit(c));
     RC(apply_reset(c, false));
     RC(commit_T_rows(c, Tp));
-    StackLnArgs a{};
-    a.src = feats; a.mode = 1; a.row_off = c->dc.row_feat_off; a.T_row = c->T_row_dev; a.ln_w = c->ln_w; a.ln_b = c->ln_b;
-    a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels; a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT;
-    a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = Tp;
-    LAUNCH_STACK_LN( dim3((Tp + 3) / 4, c->M), dim3(256), 0, c->stream, a);
+    stack_ln_feats(c, feats, c->dc.row_feat_off, c->T_row_dev, Tp);
     run_encoder(c, Tp);
     hipLaunchKernelGGL(k_enc_out, dim3(grid1((size_t)B * Tp * H)), dim3(256), 0, c->stream,
                        (const void*)c->ybuf[(d.enc_layers - 1) & 1], c->Tcap * c->MT, c->M, out, B, Tp, H, c->bf);
@@ -2100,12 +1979,8 @@ int lasr_step_window(lasr_ctx* c, const int* slots, int n, const float* pcm, int
     if (c->M > 512) return fail(c, LASR_EINVAL, "lasr_step_window supports up to 512 stream slots");
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
-    const float* src = pcm;
-    if (!is_device_ptr(pcm)) {
-        RC(ensure_buf(c, &c->stage_pcm, &c->stage_pcm_floats, (size_t)n * N));
-        HIPCHK(c, hipMemcpyAsync(c->stage_pcm, pcm, sizeof(float) * (size_t)n * N, hipMemcpyHostToDevice, c->stream));
-        src = c->stage_pcm;
-    }
+    const float* src = nullptr;
+    RC(stage_to_device(c, pcm, (size_t)n * N, &c->stage_pcm, &c->stage_pcm_floats, &src));
     long long Nw = N;
     if (sr != d.sample_rate) {                              // Resample.encodes on the whole window (transforms.py:141-144)
         int64_t No = 0;
@@ -2127,24 +2002,17 @@ int lasr_step_window(lasr_ctx* c, const int* slots, int n, const float* pcm, int
     RC(cmd_begin(c));
     std::vector<int> model_rows;
     MelArgs m{};
-    fill_mel_args(c, m);
     for (int i = 0; i < n; ++i) {
         const int s = slots[i];
         m.dst_row_v[i] = (short)s;
         m.sel_v[i] = (short)(c->n_pend[s] * d.n_stack);
         c->pend_mat[(size_t)s * d.n_buffer + c->n_pend[s]] = 1;
         c->pend_serial[(size_t)s * d.n_buffer + c->n_pend[s]] = c->n_chunks[s];
-        if (++c->n_pend[s] == d.n_buffer) {
-            c->n_pend[s] = 0;
-            c->hc.T_row[s] = d.n_buffer;
-            model_rows.push_back(s);
-        }
+        frame_collected(c, s, model_rows);
     }
     RC(cmd_commit(c));
     rec(c, 0);
-    m.pcm = src; m.N = Nw; m.stream = 0; m.by_value = 1; m.frame0 = a0; m.frames_per_row = d.n_stack;
-    m.out = c->pend; m.out_frames = d.n_buffer * d.n_stack; m.chunk = d.chunk; m.n_window = d.n_window;
-    hipLaunchKernelGGL(k_logmel, dim3((d.n_stack + 3) / 4, n), dim3(256), 0, c->stream, m);
+    launch_logmel_window(c, m, src, Nw, a0, n);
     if (model_rows.empty()) {
         HIPCHK(c, hipGetLastError());
         return LASR_OK;
@@ -2152,21 +2020,9 @@ int lasr_step_window(lasr_ctx* c, const int* slots, int n, const float* pcm, int
     const int Tm = d.n_buffer;
     RC(ensure_T(c, Tm));
     RC(commit_T_rows(c, Tm));
-    {
-        StackLnArgs a{};
-        a.src = c->pend; a.mode = 0; a.src_frames = d.n_buffer * d.n_stack; a.frame_step = d.n_stack; a.row_off = nullptr;
-        a.T_row = c->T_row_dev; a.ln_w = c->ln_w; a.ln_b = c->ln_b; a.x0 = c->x0; a.F = d.feat; a.n_mels = d.n_mels;
-        a.n_stack = d.n_stack; a.M = c->M; a.MT = c->MT; a.mt_total = c->Tcap * c->MT; a.feats_out = nullptr; a.bf = c->bf; a.Tmax = Tm;
-        LAUNCH_STACK_LN( dim3((Tm + 3) / 4, c->M), dim3(256), 0, c->stream, a);
-    }
-    rec(c, 1);
-    run_encoder(c, Tm);
-    rec(c, 2);
-    RC(run_decode(c, Tm, d.max_iters_stream, false, model_rows));
-    rec(c, 3);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    collect_stats(c, Tm);
+    stack_ln_logmel(c, c->pend, d.n_buffer * d.n_stack, d.n_stack, c->T_row_dev, Tm);
+    encode_step(c, Tm);
+    RC(decode_and_collect(c, Tm, d.max_iters_stream, false, model_rows));
     if (n_ran) *n_ran = (int)model_rows.size();
     return LASR_OK;
 }
@@ -2487,19 +2343,14 @@ int lasr_debug_fe_race(lasr_ctx* c, int iters, int aggressor, int per_iter, int 
     if (!c->fe_fused || !c->stream_dec || c->M > 512) return fail(c, LASR_ESTATE, "the race probe needs the fused front-end and the decode stream");
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
-    int nf = 0;
-    const int a0 = stream_frame0(c, &nf);
-    FeMelArgs m{};
-    m.window = c->window; m.tw512 = c->tw512; m.tw1024 = c->tw1024; m.fb_start = c->fb_start; m.fb_off = c->fb_off; m.fb_w = c->fb_w;
-    m.n_mels = d.n_mels; m.hop = d.hop; m.fb_nnz = c->fb_nnz; m.win_off = (d.n_fft - d.win) / 2; m.win_len = d.win;
-    m.pcm = c->win; m.ring_pos = c->ring_pos; m.chunk = d.chunk; m.n_window = d.n_window; m.ring_chunks = c->ring_chunks; m.frame0 = a0;
     // (outputs go to scratch buffers: the slots' pending frames and the step's frame counts stay as they are)
     const size_t n_pend = (size_t)c->M * d.n_buffer * d.n_stack * d.n_mels;
     float* pend_x = nullptr; int* trow_x = nullptr;
     RC(dalloc(c, &pend_x, n_pend));
     RC(dalloc(c, &trow_x, (size_t)c->M));
-    m.pend = pend_x; m.pend_frames = d.n_buffer * d.n_stack; m.trow_out = trow_x;
-    for (int r = 0; r < 512; ++r) { m.idx[r] = -1; m.tp_pk[r] = 0; m.age_pk[r] = 0; }
+    FeMelArgs m{};
+    fill_fe_mel_args(c, m, pend_x);
+    m.trow_out = trow_x;
     for (int r = 0; r < c->M; ++r) {
         m.tp_pk[r] = (unsigned char)((c->h_ring_pos[r] << 4) | d.n_buffer);
         unsigned pk = 0;
