@@ -224,6 +224,28 @@ int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, doub
  * instead of one per stream. */
 int lasr_fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int cap, int* n_new);
 
+/* ---- Per-token alignment records (greedy decode): when was a token emitted, and how sure was the joint.
+ * While on, every token the decode loop emits carries
+ *   frame (int32): index of the encoder frame on which it was emitted; one frame = stride * hop / sample_rate seconds (80 ms with
+ *       the reference front-end).  Counted per slot from 0 at lasr_stream_open for the streaming protocols (no lasr_stream_reset
+ *       restarts it: audio time keeps running) and from the start of the utterance for lasr_transcribe_*.  When the per-frame cap
+ *       (max_iters) is hit, all max_iters tokens carry that frame.
+ *   logp (float32): the joint's log-softmax at the joint's argmax of that decision -- the term summed into neg_logp (models.py:
+ *       420-422).  With an LM attached the token may be the fuser's re-pick; logp stays the joint's.  exp(logp) = confidence.
+ * Results, buffer sizes and launches of a context that never turns them on are untouched.
+ * Greedy decode only (LASR_EINVAL with beam > 1).  Default off.  A call that changes nothing returns LASR_OK at once; a switch
+ * needs an idle context: LASR_ESTATE while a submitted step is uncollected or a slot holds tokens that were not fetched yet. */
+int lasr_set_alignments(lasr_ctx* c, int on);
+/* lasr_fetch plus, per token, its emission frame and log p.  LASR_ESTATE if alignments are off.
+ * LASR_EFULL: nothing consumed, *n_new = needed.  neg_logp / align as in lasr_fetch (optional).
+ * lasr_fetch / lasr_fetch_many keep working on such a context: they drop the records of the tokens they hand out.
+ * lasr_peek_slot / lasr_peek_many and the native front (lasr_front_*) stay tokens-only. */
+int lasr_fetch_aligned(lasr_ctx* c, int slot, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_new,
+                       double* neg_logp, double* align);
+/* Batched form: tokens / frames / logps [n, cap], n_new [n]. */
+int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int32_t* frames, float* logps,
+                            int cap, int* n_new);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */

@@ -51,23 +51,48 @@ class LibreASR:
             pcm = self.engine.resample(torch.as_tensor(np.ascontiguousarray(pcm)[None]).to(self.engine.device), sr)[0]
         return pcm
 
-    def transcribe(self, audio, return_ids=False):
-        """Whole utterance(s): fresh state, greedy, max_iters_offline (Transcribe RPC, api-server.py:64-80)."""
+    def _want_alignment(self):
+        """Turns the engine's per-token records on (greedy decode only; a no-op when they are on already)."""
+        if self.engine.beam > 1:
+            raise NotImplementedError("return_alignment needs greedy decode: per-token alignments are not defined for beam > 1")
+        self.engine.set_alignments(True)
+
+    def _aligned(self, tokens, frames, logps):
+        """-> [(token_id, time_s, confidence)]: time_s = frame * stride * hop / sample_rate, confidence = exp(log p)."""
+        d = self.engine.desc
+        dt = d.stride * d.hop / d.sample_rate
+        return [(int(t), float(f) * dt, float(np.exp(np.float64(lp)))) for t, f, lp in zip(tokens, frames, logps)]
+
+    def transcribe(self, audio, return_ids=False, return_alignment=False):
+        """Whole utterance(s): fresh state, greedy, max_iters_offline (Transcribe RPC, api-server.py:64-80).
+        return_alignment=True: per utterance a list of (token_id, time_s, confidence) instead of text -- time_s is the start of the
+        80 ms encoder frame on which the token was emitted, confidence the joint's probability of that decision."""
         batch = audio if isinstance(audio, (list, tuple)) else [audio]
+        if return_alignment:
+            self._want_alignment()
         slots = [self.engine.open() for _ in batch]
         try:
             self.engine.transcribe_pcm(slots, [self._utterance(a) for a in batch])
-            ids = [self.engine.fetch(s)[0] for s in slots]
+            if return_alignment:
+                out = [self._aligned(*self.engine.fetch_aligned(s)[:3]) for s in slots]
+            else:
+                ids = [self.engine.fetch(s)[0] for s in slots]
         finally:
             for s in slots:
                 self.engine.close_slot(s)
-        out = ids if return_ids else [self.lang.denumericalize(i) for i in ids]
+        if not return_alignment:
+            out = ids if return_ids else [self.lang.denumericalize(i) for i in ids]
         return out if isinstance(audio, (list, tuple)) else out[0]
 
-    def stream(self, chunks, return_ids=False):
+    def stream(self, chunks, return_ids=False, return_alignment=False):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the
-        hypothesis so far after every model call."""
+        hypothesis so far after every model call.
+        return_alignment=True: yields the list of (token_id, time_s, confidence) of the hypothesis so far.  time_s is NOMINAL for a
+        stream: the streaming front-end takes each frame from the middle chunk of its 3-chunk window, so frame k * 80 ms is where
+        the frame sits in the stream of model frames, not an exact position in the client's audio."""
         eng = self.engine
+        if return_alignment:
+            self._want_alignment()
         slot = eng.open()
         y = []
         try:
@@ -81,6 +106,10 @@ class LibreASR:
                     pcm = pad
                 eng.push([slot], pcm[None] if not isinstance(pcm, torch.Tensor) else pcm[None])
                 if eng.step([slot]):
+                    if return_alignment:
+                        y = y + self._aligned(*eng.fetch_aligned(slot)[:3])
+                        yield list(y)
+                        continue
                     got = eng.fetch(slot)[0]
                     y = got if eng.beam > 1 else y + got      # beam: the whole best hypothesis
                     yield list(y) if return_ids else self.lang.denumericalize(y)

@@ -73,6 +73,28 @@ int commit_T_rows(lasr_ctx* c, int T_max, bool fixed_copy = true, int* fixed_hom
 }
 
 // ---------------------------------------------------------------------------- buffers that grow
+// The step's result blocks for c->tok_cap_alloc tokens per row (stream idle).  Device: [ntok M][tokens M x tok_cap] and, with
+// alignment records on, [frames M x tok_cap][log p M x tok_cap] behind them -- one contiguous block, packed by the step's own
+// tok_cap (run_decode), so a group's results reach the host in one copy.  Pinned: the same block behind the flag words.
+int alloc_results(lasr_ctx* c) {
+    const int M = c->M;
+    const size_t per_tok = c->align_on ? 3 : 1;
+    dfree(c, c->ds.step_ntok);
+    c->ds.step_ntok = nullptr; c->ds.step_tok = nullptr;
+    RC(dalloc0(c, &c->ds.step_ntok, (size_t)M + per_tok * (size_t)M * c->tok_cap_alloc));
+    c->ds.step_tok = c->ds.step_ntok + M;
+    // pinned result block: [0] unfinished, then ntok[M], tokens (+ records), sum_iters[M], n_ones[M], logp[M] (double)
+    if (c->res_host) (void)hipHostFree(c->res_host);
+    c->res_host = nullptr;
+    c->res_bytes = sizeof(int) * (8 + 3 * (size_t)M) + sizeof(double) * M + sizeof(int) * per_tok * (size_t)M * c->tok_cap_alloc + 64;
+    HIPCHK(c, hipHostMalloc((void**)&c->res_host, c->res_bytes));
+    memset(c->res_host, 0, c->res_bytes);
+    void* dp = nullptr;
+    HIPCHK(c, hipHostGetDevicePointer(&dp, c->res_host, 0));
+    c->res_dev = (int*)dp;
+    return LASR_OK;
+}
+
 int ensure_T(lasr_ctx* c, int T) {
     if (T <= c->Tcap) return LASR_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -86,8 +108,8 @@ int ensure_T(lasr_ctx* c, int T) {
     int cap = std::max(T, std::max(2 * c->Tcap, c->d.n_buffer));
     dfree(c, c->x0); dfree(c, c->ybuf[0]); dfree(c, c->ybuf[1]); dfree(c, c->pe_sync);
     c->pe_sync = nullptr;
-    dfree(c, c->ds.step_ntok); dfree(c, c->ds.unfinished);
-    c->x0 = c->ybuf[0] = c->ybuf[1] = c->pe = nullptr; c->ds.step_ntok = nullptr; c->ds.step_tok = nullptr; c->ds.unfinished = nullptr;
+    dfree(c, c->ds.unfinished);
+    c->x0 = c->ybuf[0] = c->ybuf[1] = c->pe = nullptr; c->ds.unfinished = nullptr;
     RC(dalloc(c, (char**)&c->x0, (size_t)cap * M * F * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[0], (size_t)cap * M * H * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[1], (size_t)cap * M * H * c->esz));
@@ -95,9 +117,7 @@ int ensure_T(lasr_ctx* c, int T) {
     c->pe = c->pe_sync;
     const int mi = std::max(c->d.max_iters_offline, c->d.max_iters_stream);
     c->tok_cap_alloc = cap * mi;
-    // [ntok M][tokens M x tok_cap]: one contiguous block so a group's results reach the host in one copy
-    RC(dalloc0(c, &c->ds.step_ntok, (size_t)M + (size_t)M * c->tok_cap_alloc));
-    c->ds.step_tok = c->ds.step_ntok + M;
+    RC(alloc_results(c));
     c->n_iter_slots = cap * mi + 8;
     RC(dalloc0(c, &c->ds.unfinished, (size_t)c->n_iter_slots));
     if (c->W > 1) {
@@ -110,16 +130,6 @@ int ensure_T(lasr_ctx* c, int T) {
     HIPCHK(c, hipMemset(c->ybuf[0], 0, (size_t)cap * M * H * c->esz));
     HIPCHK(c, hipMemset(c->ybuf[1], 0, (size_t)cap * M * H * c->esz));
     HIPCHK(c, hipMemset(c->x0, 0, (size_t)cap * M * F * c->esz));
-    // pinned result block: [0] unfinished, then ntok[M], sum_iters[M], n_ones[M], logp[M] (double), tokens
-    if (c->res_host) (void)hipHostFree(c->res_host);
-    c->res_bytes = sizeof(int) * (8 + 3 * (size_t)M) + sizeof(double) * M + sizeof(int) * (size_t)M * c->tok_cap_alloc + 64;
-    HIPCHK(c, hipHostMalloc((void**)&c->res_host, c->res_bytes));
-    memset(c->res_host, 0, c->res_bytes);
-    {
-        void* dp = nullptr;
-        HIPCHK(c, hipHostGetDevicePointer(&dp, c->res_host, 0));
-        c->res_dev = (int*)dp;
-    }
     c->Tcap = cap;
     return LASR_OK;
 }

@@ -152,7 +152,8 @@ struct lasr_ctx {
     int* c_iter = nullptr;                          // device-side iteration counter of the continuous loop
     std::map<std::tuple<int, int, int>, hipGraphExec_t> cgraphs;   // (iterations, predictor parity, LM parity) -> group
     int* cont_host = nullptr;       // pinned: [0] flag, [16..16+M) per-row frame cursors, then (after NFLY*M ints) ntok_end + token ring
-    struct PendingStep { std::vector<int> rows; int Tm; int idx; bool admitted; std::vector<int> target; const int* T_row_ptr; long long serial; };
+    struct PendingStep { std::vector<int> rows; int Tm; int idx; bool admitted; std::vector<int> target; const int* T_row_ptr; long long serial;
+                         std::vector<long long> frame_off; };   // (alignment records: per row, the global frame cursor minus the slot's own count at submit)
     std::vector<PendingStep> pending;
     std::vector<long long> h_frames_sub, h_fetched;
     std::vector<int> h_avail;       // per-row frames admitted to the decode loop (device copy: c_avail)
@@ -294,6 +295,14 @@ struct lasr_ctx {
     std::vector<int> n_chunks, n_pend;
     std::vector<std::vector<int32_t>> queue;
     std::vector<double> neg_logp, align;
+    // per-token alignment records (lasr_set_alignments; greedy decode).  While on, rqueue[slot] runs parallel to queue[slot]: every
+    // place that fills, clears or pops the one does the same to the other.
+    struct TokRec { int32_t frame; float logp; };
+    bool align_on = false;
+    std::vector<std::vector<TokRec>> rqueue;
+    std::vector<long long> slot_frames;   // encoder frames the slot has consumed since lasr_stream_open (either protocol)
+    int* align_host = nullptr;            // pinned [frames M x TOKRING][log p M x TOKRING]: k_select's record rings (allocated on first use)
+    int* c_frame_ring = nullptr; float* c_logp_ring = nullptr;      // device views of the two halves
 
     // in-job timing of the dominant kernel (lasr_cell_prof): one HIP-event pair around the encoder-cell sequence of
     // every model step, on the stream the cells are launched on; harvested lazily (ring of pairs)

@@ -224,6 +224,14 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     c->la = offline ? c->la_offline : c->la_sync;
     DecState s = c->ds;
     s.tok_cap = T_max * max_iters;
+    // alignment records (lasr_set_alignments): two more arrays of the step's own [M][tok_cap] shape right behind the tokens, so
+    // they travel in the same payload / copy; off: null pointers, the payload is what it always was
+    const bool recs = c->align_on;
+    if (recs) {
+        s.step_frame = s.step_tok + (size_t)M * s.tok_cap;
+        s.step_logp = (float*)(s.step_frame + (size_t)M * s.tok_cap);
+    }
+    const size_t n_tokw = (recs ? 3 : 1) * (size_t)M * s.tok_cap;     // ints behind ntok[M]
     const int total_cap = T_max * max_iters;
     int iter = 0;
     // iterations are launched in even-sized groups (the predictor ping-pong parity then returns to
@@ -238,7 +246,9 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     int* res = c->res_host;
     int* ntok = res + 4;
     int* toks = ntok + M;                      // contiguous with ntok, as on the device
-    int* sum_iters = toks + (size_t)M * s.tok_cap;
+    const int* frames = toks + (size_t)M * s.tok_cap;     // (records on)
+    const float* logps = (const float*)(frames + (size_t)M * s.tok_cap);
+    int* sum_iters = toks + n_tokw;
     int* n_ones = sum_iters + M;
     double* logp = (double*)(((uintptr_t)(n_ones + M) + 15) & ~uintptr_t(15));
     // (the legacy NULL stream cannot be captured: graphs then only serve the pipelined path, whose
@@ -266,7 +276,7 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
         // large token blocks): only the word comes back per group; the results are copied once at the end, behind a real
         // synchronisation.  A word that arrives by hipMemcpyAsync carries nothing but itself: no ordering against any other
         // copy is assumed anywhere (round 3's "payload copy, then flag copy" let the flag overtake the payload: tests/soak.py).
-        const int n_pay = M + M * s.tok_cap;
+        const int n_pay = M + (int)n_tokw;
         if (!offline) {
             const int nb = std::max(1, std::min(64, (n_pay + 1023) / 1024));
             hipLaunchKernelGGL(k_publish, dim3(nb), dim3(256), 0, c->stream, (const int*)c->ds.step_ntok, c->res_dev + 4, n_pay,
@@ -319,7 +329,7 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     c->stats.decode_iters = iter;
     if (offline) {
         // offline results: one copy each, read only after the stream has been synchronised
-        HIPCHK(c, hipMemcpyAsync(ntok, c->ds.step_ntok, sizeof(int) * ((size_t)M + (size_t)M * s.tok_cap), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ntok, c->ds.step_ntok, sizeof(int) * ((size_t)M + n_tokw), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(sum_iters, c->ds.sum_iters, sizeof(int) * M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(n_ones, c->ds.n_ones, sizeof(int) * M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(logp, c->ds.logp_sum, sizeof(double) * M, hipMemcpyDeviceToHost, c->stream));
@@ -328,6 +338,14 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     for (int r : rows) {
         const int n = std::min(ntok[r], s.tok_cap);
         for (int q = 0; q < n; ++q) c->queue[r].push_back(toks[(size_t)r * s.tok_cap + q]);
+        if (recs) {
+            // the kernel's frame cursor starts at 0 in every step: + the frames the slot consumed before this call (offline: the
+            // utterance starts the count)
+            const long long base = offline ? 0 : c->slot_frames[r];
+            for (int q = 0; q < n; ++q)
+                c->rqueue[r].push_back({(int32_t)(base + frames[(size_t)r * s.tok_cap + q]), logps[(size_t)r * s.tok_cap + q]});
+        }
+        c->slot_frames[r] = (offline ? 0 : c->slot_frames[r]) + c->hc.T_row[r];
         if (offline) {
             c->neg_logp[r] = -logp[r];
             // alignment_score = (sum(iters) - #frames with 1 iter) / (sum(iters) + 1e-4)  (models.py:447-453)

@@ -68,6 +68,7 @@ void lasr_destroy(lasr_ctx* c) {
     if (c->cmd_host) (void)hipHostFree(c->cmd_host);
     if (c->res_host) (void)hipHostFree(c->res_host);
     if (c->cont_host) (void)hipHostFree(c->cont_host);
+    if (c->align_host) (void)hipHostFree(c->align_host);
     for (auto& e : c->tr_ev) (void)hipEventDestroy(e);
     if (c->tr_base) (void)hipEventDestroy(c->tr_base);
     if (c->trellis_host) (void)hipHostFree(c->trellis_host);
@@ -433,6 +434,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
 
     c->open_.assign(M, 0); c->n_chunks.assign(M, 0); c->n_pend.assign(M, 0);
     c->queue.assign(M, {}); c->neg_logp.assign(M, 0.0); c->align.assign(M, 0.0);
+    c->rqueue.assign(M, {}); c->slot_frames.assign(M, 0);
     c->ev_ok = true;
     for (auto& e : c->ev)
         if (hipEventCreate(&e) != hipSuccess) c->ev_ok = false;
@@ -494,6 +496,7 @@ int lasr_stream_open(lasr_ctx* c, int* slot) {
     for (int s = 0; s < c->d.max_streams; ++s)
         if (!c->open_[s]) {
             c->open_[s] = 1;
+            c->slot_frames[s] = 0;             // the per-slot frame index of the alignment records starts here (no reset restarts it)
             *slot = s;
             return lasr_stream_reset(c, s, 1 | 2 | 4 | 8);
         }
@@ -531,7 +534,7 @@ static int reset_impl(lasr_ctx* c, const int* slots, int n, int what) {
     if (what & 8) RC(flush_lazy(c));         // (the PCM ring of these slots starts over)
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
-        if (what & 8) { c->n_chunks[slot] = 0; c->n_pend[slot] = 0; c->queue[slot].clear(); c->neg_logp[slot] = 0.0; }
+        if (what & 8) { c->n_chunks[slot] = 0; c->n_pend[slot] = 0; c->queue[slot].clear(); c->rqueue[slot].clear(); c->neg_logp[slot] = 0.0; }
         if (what & 2) beam_host_reset(c, slot, (what & 8) != 0);
     }
     if (what & 7) {
@@ -577,7 +580,7 @@ int lasr_stream_close(lasr_ctx* c, int slot) {
         if (std::find(p.rows.begin(), p.rows.end(), slot) != p.rows.end())
             return fail(c, LASR_ESTATE, "slot %d has a submitted step in flight: call lasr_step_wait first", slot);
     c->open_[slot] = 0;
-    c->queue[slot].clear();
+    c->queue[slot].clear(); c->rqueue[slot].clear();
     return LASR_OK;
 }
 
@@ -1116,7 +1119,14 @@ static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fuse
     p.T_row_ptr = c->T_row_dev;             // lives in the command ring until long after this step is collected
     p.serial = c->model_steps;
     p.target.assign(c->M, 0);
-    for (int r : model_rows) { c->h_frames_sub[r] += Tm; p.target[r] = (int)c->h_frames_sub[r]; }
+    p.frame_off.assign(c->M, 0);
+    for (int r : model_rows) {
+        // alignment records: the continuous loop's frame cursor is global per row; what the slot has consumed since it was opened
+        // is not (no step of the row is in flight while the difference changes: open and the synchronous steps need an idle slot)
+        p.frame_off[r] = c->h_frames_sub[r] - c->slot_frames[r];
+        c->slot_frames[r] += Tm;
+        c->h_frames_sub[r] += Tm; p.target[r] = (int)c->h_frames_sub[r];
+    }
     bool kicked = false;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -1143,6 +1153,12 @@ static long long step_end_mark(const lasr_ctx* c, const lasr_ctx::PendingStep& P
 static int32_t ring_token(const lasr_ctx* c, int r, long long q) {
     const int* h_ring = c->cont_host + 16 + (size_t)(lasr_ctx::NFLY + lasr_ctx::ENDSLOTS) * c->M;
     return h_ring[(size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)];
+}
+// its alignment record (alignments on): the same ring position of the two record rings, the frame as the slot counts it
+static lasr_ctx::TokRec ring_record(const lasr_ctx* c, const lasr_ctx::PendingStep& P, int r, long long q) {
+    const size_t at = (size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING);
+    const float* h_logp = (const float*)(c->align_host + (size_t)c->M * lasr_ctx::TOKRING);
+    return {(int32_t)(c->align_host[at] - P.frame_off[r]), h_logp[at]};
 }
 
 // The submitted, uncollected steps of one slot, oldest first (c->mu held, cursors polled): *n_inflight counts them, *n_decoded the
@@ -1255,6 +1271,7 @@ static void cont_states(lasr_ctx* c, DecState& s, BeamState& bs) {
     s = c->ds;
     s.t_idx = c->c_cur; s.iters = c->c_iters; s.step_ntok = c->c_ntotal; s.step_tok = c->c_tok_ring;
     s.tok_cap = lasr_ctx::TOKRING; s.unfinished = c->c_behind; s.cont = 1; s.host_cur = c->c_hcur_dev;
+    s.step_frame = c->align_on ? c->c_frame_ring : nullptr; s.step_logp = c->align_on ? c->c_logp_ring : nullptr;
     s.host_ntot = c->tr_on ? c->c_hcur_dev + M : nullptr;
     s.ntok_end = c->c_ntok_end; s.step_T = c->d.n_buffer; s.end_slots = lasr_ctx::ENDSLOTS; s.done_blocks = c->c_done;
     s.iter_ctr = c->c_iter;
@@ -1692,6 +1709,8 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
     for (int r : P.rows) {
         const long long end = step_end_mark(c, P, r);
         for (long long q = c->h_fetched[r]; q < end; ++q) c->queue[r].push_back(ring_token(c, r, q));
+        if (c->align_on)
+            for (long long q = c->h_fetched[r]; q < end; ++q) c->rqueue[r].push_back(ring_record(c, P, r, q));
         c->h_fetched[r] = end;
     }
     c->stats.frames = P.Tm;
@@ -1736,7 +1755,7 @@ int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, 
         c->hc.T_row[s] = Tp[i]; c->hc.what[s] = 7; c->hc.row_frames[s] = Tm[i];
         c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
         off += n_samples[i];
-        c->queue[s].clear();
+        c->queue[s].clear(); c->rqueue[s].clear();
         c->neg_logp[s] = 0.0;
         beam_host_reset(c, s, true);
     }
@@ -1773,7 +1792,7 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
         const int s = slots[i];
         c->hc.T_row[s] = n_frames[i]; c->hc.what[s] = 7; c->hc.row_feat_off[s] = off;
         off += n_frames[i];
-        c->queue[s].clear();
+        c->queue[s].clear(); c->rqueue[s].clear();
         c->neg_logp[s] = 0.0;
         beam_host_reset(c, s, true);
     }
@@ -1821,7 +1840,7 @@ int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, doub
     }
     if (!q.empty()) memcpy(tokens, q.data(), sizeof(int32_t) * q.size());
     *n_new = (int)q.size();
-    q.clear();
+    q.clear(); c->rqueue[slot].clear();       // (the records of tokens handed out without them are dropped)
     if (neg_logp) *neg_logp = c->neg_logp[slot];
     if (align) *align = c->align[slot];
     return LASR_OK;
@@ -1838,7 +1857,85 @@ int lasr_fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int c
         auto& q = c->queue[slots[i]];
         if (!q.empty()) memcpy(tokens + (size_t)i * cap, q.data(), sizeof(int32_t) * q.size());
         n_new[i] = (int)q.size();
-        q.clear();
+        q.clear(); c->rqueue[slots[i]].clear();
+    }
+    return LASR_OK;
+}
+
+// ---------------------------------------------------------------------------- per-token alignment records
+// Greedy decode: k_select stores, next to every token, the frame cursor and the joint's log p of that decision (DecState::
+// step_frame / step_logp; null pointers = off, the default).  Toggling changes what the decode launches store and how the
+// synchronous result block is laid out, so the engine must be idle, and every cached decode graph (DecState is captured by
+// value) is dropped.
+int lasr_set_alignments(lasr_ctx* c, int on) {
+    if (!c) return LASR_EINVAL;
+    if (c->W > 1) return fail(c, LASR_EINVAL, "alignment records serve greedy decode (beam = 1)");
+    const bool want = on != 0;
+    if (want == c->align_on) return LASR_OK;       // (nothing to switch: also fine while steps are in flight)
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    // tokens decoded before the switch would have no record (on) or lose theirs (off): they are fetched first, so that
+    // queue[slot] and rqueue[slot] are parallel whenever records are on
+    for (int s = 0; s < c->M; ++s)
+        if (!c->queue[s].empty()) return fail(c, LASR_ESTATE, "slot %d has %d unfetched token(s): fetch them before the switch", s, (int)c->queue[s].size());
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    {
+        std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
+        for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
+        c->graphs.clear();
+        for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
+        c->cgraphs.clear();
+    }
+    if (want && !c->align_host) {
+        const size_t n = (size_t)c->M * lasr_ctx::TOKRING;
+        HIPCHK(c, hipHostMalloc((void**)&c->align_host, sizeof(int) * 2 * n));
+        memset(c->align_host, 0, sizeof(int) * 2 * n);
+        void* dp = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&dp, c->align_host, 0));
+        c->c_frame_ring = (int*)dp;
+        c->c_logp_ring = (float*)((int*)dp + n);
+    }
+    c->align_on = want;
+    RC(alloc_results(c));
+    return LASR_OK;
+}
+
+int lasr_fetch_aligned(lasr_ctx* c, int slot, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_new, double* neg_logp,
+                       double* align) {
+    if (!c || !n_new) return LASR_EINVAL;
+    if (!c->align_on) return fail(c, LASR_ESTATE, "alignment records are off: call lasr_set_alignments first");
+    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
+    auto& q = c->queue[slot];
+    auto& rq = c->rqueue[slot];
+    if ((int)q.size() > cap || ((!tokens || !frames || !logps) && !q.empty())) {
+        *n_new = (int)q.size();
+        return fail(c, LASR_EFULL, "token buffer too small: need %d", (int)q.size());
+    }
+    for (size_t i = 0; i < q.size(); ++i) { tokens[i] = q[i]; frames[i] = rq[i].frame; logps[i] = rq[i].logp; }
+    *n_new = (int)q.size();
+    q.clear(); rq.clear();
+    if (neg_logp) *neg_logp = c->neg_logp[slot];
+    if (align) *align = c->align[slot];
+    return LASR_OK;
+}
+
+int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_new) {
+    if (!c || !n_new || (n > 0 && (!slots || !tokens || !frames || !logps))) return LASR_EINVAL;
+    if (!c->align_on) return fail(c, LASR_ESTATE, "alignment records are off: call lasr_set_alignments first");
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots[i];
+        if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
+        if ((int)c->queue[slot].size() > cap) return fail(c, LASR_EFULL, "token buffer too small: slot %d needs %d", slot, (int)c->queue[slot].size());
+    }
+    for (int i = 0; i < n; ++i) {
+        auto& q = c->queue[slots[i]];
+        auto& rq = c->rqueue[slots[i]];
+        const size_t o = (size_t)i * cap;
+        for (size_t j = 0; j < q.size(); ++j) { tokens[o + j] = q[j]; frames[o + j] = rq[j].frame; logps[o + j] = rq[j].logp; }
+        n_new[i] = (int)q.size();
+        q.clear(); rq.clear();
     }
     return LASR_OK;
 }

@@ -229,6 +229,9 @@ struct DecState {
     int* step_ntok;    // [M] tokens emitted in this step
     int* step_tok;     // [M][tok_cap]
     int tok_cap;
+    // per-token alignment records (lasr_set_alignments), indexed like step_tok; nullptr (both): off, nothing is stored
+    int* step_frame;   // [M][tok_cap] frame cursor of the row when the token was emitted (step-relative; continuous mode: global)
+    float* step_logp;  // [M][tok_cap] the joint's log-softmax at its argmax of that decision (the term added to logp_sum)
     double* logp_sum;  // [M] sum of log p of every decision (models.py:420-422)
     int* sum_iters;    // [M] evaluations in this step
     int* n_ones;       // [M] frames finished after exactly one evaluation (alignment_score)
@@ -640,8 +643,14 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
             emitted = 1;
             if (tid == 0) {
                 const int tok = tok_e;               // (k == ke: the first non-blank frame, re-picked above when an LM is attached)
-                if (s.cont) s.step_tok[(size_t)r * s.tok_cap + (n0 % s.tok_cap)] = tok;
-                else if (n0 < s.tok_cap) s.step_tok[(size_t)r * s.tok_cap + n0] = tok;
+                const int at = s.cont ? n0 % s.tok_cap : n0;
+                if (at < s.tok_cap) {
+                    s.step_tok[(size_t)r * s.tok_cap + at] = tok;
+                    if (s.step_frame) {              // alignments on (uniform over the launch): t is the EMITTING frame, logp[k] the joint's
+                        s.step_frame[(size_t)r * s.tok_cap + at] = t;
+                        s.step_logp[(size_t)r * s.tok_cap + at] = logp[k];
+                    }
+                }
                 n0 += 1;
                 s.token[r] = tok;
             }

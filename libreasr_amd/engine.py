@@ -293,6 +293,36 @@ class Engine:
         rows = buf[:, :mx].tolist()          # (one conversion of the occupied columns instead of a slice + tolist per slot)
         return [r[:c] for r, c in zip(rows, cl)]
 
+    # ------------------------------------------------------------------ per-token alignment records
+    def set_alignments(self, on=True):
+        """Per-token emission frame and log p from greedy decode (lasr_set_alignments): off by default; to switch, the engine
+        must be idle (no submitted step uncollected, no token unfetched).  beam > 1: LasrError (LASR_EINVAL)."""
+        self._chk(self.lib.lasr_set_alignments(self.ctx, 1 if on else 0))
+
+    def fetch_aligned(self, slot, cap=65536):
+        """fetch(slot) plus the records -> (tokens, frames, logps, neg_logp, align): frames[i] = encoder frame (since open / start
+        of the utterance) on which tokens[i] was emitted, logps[i] = the joint's log p of that decision (float32 arrays)."""
+        tok = np.empty(cap, dtype=np.int32)
+        fr = np.empty(cap, dtype=np.int32)
+        lp = np.empty(cap, dtype=np.float32)
+        n = C.c_int(0)
+        nl, al = C.c_double(0.0), C.c_double(0.0)
+        self._chk(self.lib.lasr_fetch_aligned(self.ctx, int(slot), tok.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p),
+                                              lp.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(nl), C.byref(al)))
+        k = n.value
+        return [int(v) for v in tok[:k]], fr[:k].copy(), lp[:k].copy(), nl.value, al.value
+
+    def fetch_many_aligned(self, slots, cap=256):
+        """fetch_many plus the records -> list of (tokens, frames, logps) per listed slot."""
+        a, p, n = self._slots(slots)
+        tok = np.empty((n, cap), dtype=np.int32)
+        fr = np.empty((n, cap), dtype=np.int32)
+        lp = np.empty((n, cap), dtype=np.float32)
+        cnt = np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.lasr_fetch_many_aligned(self.ctx, p, n, tok.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p),
+                                                   lp.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
+        return [(tok[i, :k].tolist(), fr[i, :k].copy(), lp[i, :k].copy()) for i, k in enumerate(cnt.tolist())]
+
     # ------------------------------------------------------------------ offline
     def transcribe_pcm(self, slots, pcm_list):
         """pcm_list: list of 1-D float32 arrays/tensors (one utterance per slot)."""
