@@ -70,7 +70,9 @@ typedef struct {
                          /* vocab <= 2048 (a hypothesis row's logits live in one wave).  */
                          /* lasr_fetch then returns the WHOLE current best hypothesis    */
                          /* after every model step (it may change retroactively),        */
-                         /* neg_logp = -its score, align = 0.  Both protocols (the        */
+                         /* neg_logp = -its score, align = 0; lasr_set_beam_records +     */
+                         /* lasr_fetch_nbest: the whole beam with per-token frame and     */
+                         /* log p.  Both protocols (the                                   */
                          /* pipelined one: <= 512 stream slots); an attached LM is fused  */
                          /* inside the beam (see lasr_attach_lm).                         */
 } lasr_model_desc;
@@ -245,6 +247,30 @@ int lasr_fetch_aligned(lasr_ctx* c, int slot, int32_t* tokens, int32_t* frames, 
 /* Batched form: tokens / frames / logps [n, cap], n_new [n]. */
 int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int32_t* frames, float* logps,
                             int cap, int* n_new);
+
+/* ---- Beam search (beam > 1): the whole beam per model step, every token with its emission frame and log p.
+ * While on, the result of every model step is every alive hypothesis, best first, and every token of every hypothesis carries
+ *   frame (int32): as for lasr_set_alignments -- counted per slot from 0 at lasr_stream_open (no lasr_stream_reset restarts it), from
+ *       the start of the utterance for lasr_transcribe_*; at most max_iters tokens of a hypothesis sit on one frame.
+ *   logp (float32): the joint's log-softmax of that extension -- the f32 term the beam added to the hypothesis's score.  With an LM
+ *       attached the token is the fuser's re-pick; logp stays the joint's for the best non-blank token.  exp(logp) = confidence.
+ * After a predictor reset (lasr_stream_reset bit 2) the best hypothesis is frozen with its records; every hypothesis handed out
+ * afterwards is that prefix followed by a hypothesis of the restarted beam.  Tokens decoded before a switch-on have frame -1, logp 0.
+ * Allocations, kernels and results of a context that never turns them on are untouched.
+ * beam > 1 only (LASR_EINVAL on a greedy context: that one has lasr_set_alignments).  Default off.  A call that changes nothing
+ * returns LASR_OK at once; a switch needs an idle context (LASR_ESTATE while a submitted step is uncollected or a slot holds a
+ * result that was not fetched), and drops the cached decode graphs. */
+int lasr_set_beam_records(lasr_ctx* c, int on);
+/* lasr_fetch for a beam context, whole beam: consumes what lasr_fetch would have consumed.  Up to max_hyps hypotheses, best first
+ * (score descending, then slot ascending); no merging: two hypotheses may hold the same tokens on different frames.
+ * tokens / frames / logps: [max_hyps][cap] (frames, logps optional); n_tokens [max_hyps]; scores [max_hyps] = sum of log p of every
+ * decision incl. blanks (scores[0] == -neg_logp of lasr_fetch); *n_hyps = hypotheses alive (may exceed max_hyps: the rest is dropped).
+ * Hypothesis 0 is exactly what lasr_fetch returns.  With max_hyps > 0, tokens, n_tokens and scores are required (LASR_EINVAL if null);
+ * max_hyps == 0 drops the result and reports *n_hyps.  LASR_ESTATE if the switch is off; LASR_EFULL (a hypothesis is longer than cap):
+ * nothing consumed, n_tokens[i] = needed for i < min(max_hyps, *n_hyps), *n_hyps set; call again with cap >= the largest of them.
+ * lasr_fetch / lasr_fetch_many keep working on such a context: they drop the rest of the beam with the result they hand out. */
+int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32_t* frames, float* logps, int cap,
+                     int* n_tokens, double* scores, int* n_hyps);
 
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */

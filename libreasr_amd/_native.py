@@ -69,6 +69,8 @@ SYMBOLS = [
     ("lasr_fetch_aligned", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double)]),
     ("lasr_fetch_many_aligned", C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
+    ("lasr_set_beam_records", C.c_int, [_P, C.c_int]),
+    ("lasr_fetch_nbest", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_int)]),
     ("lasr_logmel", C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     ("lasr_stack", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     ("lasr_encoder", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

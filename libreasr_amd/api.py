@@ -54,7 +54,8 @@ class LibreASR:
     def _want_alignment(self):
         """Turns the engine's per-token records on (greedy decode only; a no-op when they are on already)."""
         if self.engine.beam > 1:
-            raise NotImplementedError("return_alignment needs greedy decode: per-token alignments are not defined for beam > 1")
+            raise NotImplementedError("return_alignment needs greedy decode; a beam engine returns its hypotheses with per-token "
+                                      "times and confidences through nbest=k")
         self.engine.set_alignments(True)
 
     def _aligned(self, tokens, frames, logps):
@@ -63,36 +64,58 @@ class LibreASR:
         dt = d.stride * d.hop / d.sample_rate
         return [(int(t), float(f) * dt, float(np.exp(np.float64(lp)))) for t, f, lp in zip(tokens, frames, logps)]
 
-    def transcribe(self, audio, return_ids=False, return_alignment=False):
+    def _want_nbest(self, nbest):
+        """Turns the engine's whole-beam results on (beam search only; a no-op when they are on already)."""
+        if self.engine.beam <= 1:
+            raise ValueError("nbest= needs a beam engine (beam > 1); greedy decode has return_alignment=True")
+        if int(nbest) < 1:
+            raise ValueError("nbest must be >= 1")
+        self.engine.set_beam_records(True)
+
+    def _nbest(self, slot, k):
+        """-> up to k hypotheses, best first: {"score": sum of log p of every decision, "tokens": [(token_id, time_s, confidence)]}"""
+        return [{"score": sc, "tokens": self._aligned(t, f, lp)} for t, f, lp, sc in self.engine.fetch_nbest(slot, int(k))]
+
+    def transcribe(self, audio, return_ids=False, return_alignment=False, nbest=None):
         """Whole utterance(s): fresh state, greedy, max_iters_offline (Transcribe RPC, api-server.py:64-80).
         return_alignment=True: per utterance a list of (token_id, time_s, confidence) instead of text -- time_s is the start of the
-        80 ms encoder frame on which the token was emitted, confidence the joint's probability of that decision."""
+        80 ms encoder frame on which the token was emitted, confidence the joint's probability of that decision.  Greedy decode;
+        a beam engine raises NotImplementedError: use nbest=.
+        nbest=k (beam engines; ValueError on a greedy one): per utterance up to k hypotheses of the final beam, best first, each
+        {"score": float, "tokens": [(token_id, time_s, confidence)]} with time_s / confidence as above; no merging, no length norm."""
         batch = audio if isinstance(audio, (list, tuple)) else [audio]
         if return_alignment:
             self._want_alignment()
+        if nbest is not None:
+            self._want_nbest(nbest)
         slots = [self.engine.open() for _ in batch]
         try:
             self.engine.transcribe_pcm(slots, [self._utterance(a) for a in batch])
-            if return_alignment:
+            if nbest is not None:
+                out = [self._nbest(s, nbest) for s in slots]
+            elif return_alignment:
                 out = [self._aligned(*self.engine.fetch_aligned(s)[:3]) for s in slots]
             else:
                 ids = [self.engine.fetch(s)[0] for s in slots]
         finally:
             for s in slots:
                 self.engine.close_slot(s)
-        if not return_alignment:
+        if not return_alignment and nbest is None:
             out = ids if return_ids else [self.lang.denumericalize(i) for i in ids]
         return out if isinstance(audio, (list, tuple)) else out[0]
 
-    def stream(self, chunks, return_ids=False, return_alignment=False):
+    def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the
         hypothesis so far after every model call.
         return_alignment=True: yields the list of (token_id, time_s, confidence) of the hypothesis so far.  time_s is NOMINAL for a
         stream: the streaming front-end takes each frame from the middle chunk of its 3-chunk window, so frame k * 80 ms is where
-        the frame sits in the stream of model frames, not an exact position in the client's audio."""
+        the frame sits in the stream of model frames, not an exact position in the client's audio.
+        nbest=k (beam engines): yields up to k hypotheses of the beam after that model call, as transcribe(nbest=k) returns them."""
         eng = self.engine
         if return_alignment:
             self._want_alignment()
+        if nbest is not None:
+            self._want_nbest(nbest)
         slot = eng.open()
         y = []
         try:
@@ -106,6 +129,9 @@ class LibreASR:
                     pcm = pad
                 eng.push([slot], pcm[None] if not isinstance(pcm, torch.Tensor) else pcm[None])
                 if eng.step([slot]):
+                    if nbest is not None:
+                        yield self._nbest(slot, nbest)
+                        continue
                     if return_alignment:
                         y = y + self._aligned(*eng.fetch_aligned(slot)[:3])
                         yield list(y)

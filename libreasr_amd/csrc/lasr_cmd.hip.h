@@ -10,9 +10,14 @@ void launch_beam_select(lasr_ctx* c, BeamState& b, int iter_slot) {
     b.lm_on = c->lm.on ? 1 : 0; b.done2 = c->c_done2;
     const float* lg = (const float*)c->logits;
     // one wave per hypothesis row (k_beam_select_rw; V <= 2048 is checked at lasr_create for beam > 1)
-    if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2>), dim3(M), dim3(128), 0, c->stream, lg, b, iter_slot);
-    else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4>), dim3(M), dim3(256), 0, c->stream, lg, b, iter_slot);
-    else hipLaunchKernelGGL((k_beam_select_rw<8>), dim3(M), dim3(512), 0, c->stream, lg, b, iter_slot);
+    // (b.rec: per-token records, lasr_set_beam_records -- an instantiation of their own, so "off" runs the kernel it always ran)
+    if (b.rec) {
+        if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, true>), dim3(M), dim3(128), 0, c->stream, lg, b, iter_slot);
+        else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, true>), dim3(M), dim3(256), 0, c->stream, lg, b, iter_slot);
+        else hipLaunchKernelGGL((k_beam_select_rw<8, true>), dim3(M), dim3(512), 0, c->stream, lg, b, iter_slot);
+    } else if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, false>), dim3(M), dim3(128), 0, c->stream, lg, b, iter_slot);
+    else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, false>), dim3(M), dim3(256), 0, c->stream, lg, b, iter_slot);
+    else hipLaunchKernelGGL((k_beam_select_rw<8, false>), dim3(M), dim3(512), 0, c->stream, lg, b, iter_slot);
     if (c->lm.on)
         LAUNCH_BEAM_FUSE(c->d.vocab, dim3(c->Md), dim3(256), 0, c->stream, (const float*)c->logits, b, iter_slot, cur_lmz(c), cur_lm_valid(c),
                            c->lm.alpha, c->lm.theta, c->lm.min_val);
@@ -95,6 +100,25 @@ int alloc_results(lasr_ctx* c) {
     return LASR_OK;
 }
 
+// per-token records of the beam (lasr_set_beam_records), synchronous and offline steps: [n_iter_slots][Md] beside b_trellis, and the
+// pinned block they are copied to once per step (stream idle).  They exist exactly while the switch is on: switch-on allocates them
+// for the trellis as it is then, ensure_T regrows them with it, switch-off frees them, so they never lag behind n_iter_slots
+// (rec_slots says what they hold; run_decode_beam checks it).
+void free_beam_recs(lasr_ctx* c) {
+    dfree(c, c->b_rec); c->b_rec = nullptr;
+    if (c->rec_host) (void)hipHostFree(c->rec_host);
+    c->rec_host = nullptr;
+    c->rec_slots = 0;
+}
+int alloc_beam_recs(lasr_ctx* c) {
+    free_beam_recs(c);
+    if (c->n_iter_slots <= 0) return LASR_OK;              // (nothing has run yet: ensure_T allocates with the trellis)
+    RC(dalloc(c, &c->b_rec, (size_t)c->n_iter_slots * c->Md));
+    HIPCHK(c, hipHostMalloc((void**)&c->rec_host, sizeof(BeamRec) * (size_t)c->n_iter_slots * c->Md));
+    c->rec_slots = c->n_iter_slots;
+    return LASR_OK;
+}
+
 int ensure_T(lasr_ctx* c, int T) {
     if (T <= c->Tcap) return LASR_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -126,6 +150,7 @@ int ensure_T(lasr_ctx* c, int T) {
         if (c->trellis_host) (void)hipHostFree(c->trellis_host);
         c->trellis_host_ints = (size_t)c->n_iter_slots * c->Md + 4 * (size_t)c->Md + 16;
         HIPCHK(c, hipHostMalloc((void**)&c->trellis_host, sizeof(int) * c->trellis_host_ints));
+        if (c->beam_rec_on) RC(alloc_beam_recs(c));
     }
     HIPCHK(c, hipMemset(c->ybuf[0], 0, (size_t)cap * M * H * c->esz));
     HIPCHK(c, hipMemset(c->ybuf[1], 0, (size_t)cap * M * H * c->esz));

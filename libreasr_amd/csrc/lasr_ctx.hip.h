@@ -60,9 +60,8 @@ struct lasr_ctx {
     // beam search: c, BN(h) and pp ping-pong like h (every slot may be re-parented each round): pred_c / pred_y / pp are indexed
     // by parity and follow pred_par (par_rd / par_wr below); index 1 exists with a beam only
     double* b_score = nullptr; int *b_alive = nullptr, *b_inB = nullptr, *b_parent = nullptr, *b_trellis = nullptr;
-    // host: token history of every hypothesis slot as a shared-prefix tree per stream (a round re-parents W slots: copying W
-    // token vectors per round grows with the length of the stream; a node per emitted token does not)
-    struct BeamHost { std::vector<int> par, tok; std::vector<int> cur; };
+    // host: token history of every hypothesis slot as a shared-prefix tree per stream (lasr_beamhist.hip.h)
+    using BeamHost = ::BeamHost;
     std::vector<BeamHost> bh;
     // continuous beam loop (lasr_step_submit / lasr_step_wait with beam > 1): pinned rings written by k_beam_select
     static constexpr int TRING = 128;
@@ -72,7 +71,19 @@ struct lasr_ctx {
     int *b_endal_host = nullptr, *b_endal_dev = nullptr;     // [M][ENDSLOTS]    alive mask
     long long b_rounds_replayed = 0;
     std::vector<long long> b_frames_done;                    // per stream: frames the host has seen finished
-    struct BeamResult { std::vector<int32_t> tokens; double score; };
+    // per-token records + whole-beam results (lasr_set_beam_records / lasr_fetch_nbest).  Off (the default): no
+    // allocation, BeamState::rec null, every vector below stays empty.  On: a finished model step's result is every alive
+    // hypothesis, best first (score descending, then slot ascending), as MATERIALISED lists (committed prefix + path of the tree).
+    struct BeamHyp { std::vector<int32_t> tokens; std::vector<BeamRec> recs; double score; };
+    bool beam_rec_on = false;
+    BeamRec* b_rec = nullptr;                                // device [n_iter_slots][Md], beside b_trellis (synchronous / offline steps)
+    BeamRec* rec_host = nullptr;                             // pinned: its copy, once per step
+    int rec_slots = 0;                                       // rounds both were sized for (== n_iter_slots while the switch is on, else 0)
+    BeamRec *b_rec_ring_host = nullptr, *b_rec_ring_dev = nullptr;   // pinned [TRING][Md], beside b_tre_host (allocated at the first switch-on)
+    std::vector<long long> b_frame_off;                      // per stream: global frame cursor minus the slot's own count (set at submit, under mu)
+    std::vector<std::vector<BeamHyp>> nbest;                 // per slot: the beam of the last collected model step, until fetched
+    std::vector<std::vector<BeamRec>> committed_recs, best_recs;     // parallel to committed / best_full
+    struct BeamResult { std::vector<int32_t> tokens; double score; std::vector<BeamHyp> nbest; std::vector<BeamRec> recs; };   // recs: only when nbest is empty
     std::vector<std::deque<BeamResult>> b_results;           // per stream: finished model steps not yet collected
     std::vector<std::vector<int32_t>> committed;          // host: best hypothesis at the last predictor reset(s)
     std::vector<double> committed_score;

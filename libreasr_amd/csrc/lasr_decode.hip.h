@@ -186,32 +186,23 @@ void run_encoder(lasr_ctx* c, int T_max) {
     launch_linear<false, 3>(c, J / 16, T_max * c->MT, g, H, ea);
 }
 
-// ---- host side of the beam: hypotheses as a shared-prefix tree per stream
-void bh_reset(lasr_ctx::BeamHost& B, int W) { B.par.clear(); B.tok.clear(); B.cur.assign(W, -1); }
-void bh_tokens(const lasr_ctx::BeamHost& B, int node, std::vector<int32_t>& out) {      // appends root -> leaf
-    const size_t at = out.size();
-    for (int n = node; n >= 0; n = B.par[n]) out.push_back(B.tok[n]);
-    std::reverse(out.begin() + at, out.end());
-}
-// one selection round of a stream: e[j] = (parent slot << 16) | (token + 1 if extended else 0); -2 dead slot
-void bh_apply(lasr_ctx::BeamHost& B, const int* e, int W) {
-    int nh[8];
-    for (int j = 0; j < W; ++j) {
-        if (e[j] < 0) { nh[j] = -1; continue; }
-        const int p = B.cur[e[j] >> 16], tok = e[j] & 0xffff;
-        if (tok) { B.par.push_back(p); B.tok.push_back(tok - 1); nh[j] = (int)B.par.size() - 1; }
-        else nh[j] = p;
-    }
-    for (int j = 0; j < W; ++j) B.cur[j] = nh[j];
-    if (B.par.size() > (size_t)1 << 18) {           // compaction: keep the live hypotheses only
-        std::vector<std::vector<int32_t>> live(W);
-        for (int j = 0; j < W; ++j) bh_tokens(B, B.cur[j], live[j]);
-        B.par.clear(); B.tok.clear();
-        for (int j = 0; j < W; ++j) {
-            int n = -1;
-            for (int32_t t : live[j]) { B.par.push_back(n); B.tok.push_back(t); n = (int)B.par.size() - 1; }
-            B.cur[j] = n;
-        }
+// ---- host side of the beam: hypotheses as a shared-prefix tree per stream: lasr_beamhist.hip.h (bh_reset / bh_tokens / bh_records /
+// bh_apply).  Records on: the whole beam of stream r at the end of a model step -- every alive slot, score descending, ties by slot
+// ascending (the order in which the `best` loops pick their winner: hypothesis 0 is lasr_fetch's), each the committed prefix
+// followed by the slot's path; scores include committed_score.
+void beam_whole(lasr_ctx* c, int r, const double* sc, const char* alive, std::vector<lasr_ctx::BeamHyp>& out) {
+    const int W = c->W;
+    int ord[8], n = 0;
+    for (int j = 0; j < W; ++j)
+        if (alive[j]) ord[n++] = j;
+    std::stable_sort(ord, ord + n, [&](int a, int b) { return sc[a] > sc[b]; });
+    const auto& H = c->bh[r];
+    out.clear(); out.resize(n);
+    for (int i = 0; i < n; ++i) {
+        auto& h = out[i];
+        h.tokens = c->committed[r]; h.recs = c->committed_recs[r];
+        bh_tokens(H, H.cur[ord[i]], h.tokens); bh_records(H, H.cur[ord[i]], h.recs);
+        h.score = c->committed_score[r] + sc[ord[i]];
     }
 }
 
@@ -366,8 +357,13 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
     b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit;
     b.parent = c->b_parent; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
     b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer
+    const bool recs = c->beam_rec_on;
+    b.rec = recs ? c->b_rec : nullptr;
     const int total_cap = T_max * max_iters;
     if (total_cap + 1 > c->n_iter_slots) return fail(c, LASR_EINVAL, "decode iteration budget exceeds the trellis");
+    // the records are indexed like the trellis: they must hold as many rounds as it does
+    if (recs && (!c->b_rec || !c->rec_host || c->rec_slots != c->n_iter_slots))
+        return fail(c, LASR_ESTATE, "beam records are on but their buffers hold %d rounds, the trellis %d", c->rec_slots, c->n_iter_slots);
     int* res = c->res_host;
     hipLaunchKernelGGL(k_beam_begin, dim3(grid1(std::max(Md, c->n_iter_slots))), dim3(256), 0, c->stream, b, M, c->n_iter_slots);
     hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)Md * J)), dim3(256), 0, c->stream, (const float*)c->pe, (const float*)cur_pp(c),
@@ -404,14 +400,19 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
     HIPCHK(c, hipMemcpyAsync(tre, c->b_trellis, sizeof(int) * (size_t)iter * Md, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(sc, c->b_score, sizeof(double) * Md, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(alive, c->b_alive, sizeof(int) * Md, hipMemcpyDeviceToHost, c->stream));
+    if (recs) HIPCHK(c, hipMemcpyAsync(c->rec_host, c->b_rec, sizeof(BeamRec) * (size_t)iter * Md, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int r : rows) {
         auto& H = c->bh[r];
+        // the kernel's frame cursor starts at 0 in every step: + the frames the slot consumed before this call (offline: the
+        // utterance starts the count), as in run_decode
+        const long long base = offline ? 0 : c->slot_frames[r];
         for (int it = 0; it < iter; ++it) {
             const int* e = tre + (size_t)it * Md + (size_t)r * W;
             if (e[0] == -1) continue;                          // stream idle in this round
-            bh_apply(H, e, W);
+            bh_apply(H, e, W, recs ? c->rec_host + (size_t)it * Md + (size_t)r * W : nullptr, base);
         }
+        c->slot_frames[r] = base + c->hc.T_row[r];
         int best = -1;
         for (int j = 0; j < W; ++j)
             if (alive[(size_t)r * W + j] && (best < 0 || sc[(size_t)r * W + j] > sc[(size_t)r * W + best])) best = j;
@@ -420,6 +421,12 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
         double score = c->committed_score[r];
         if (best >= 0) { bh_tokens(H, H.cur[best], q); score += sc[(size_t)r * W + best]; }
         c->queue[r] = q;                                       // beam mode: lasr_fetch hands out the whole best hypothesis
+        if (recs) {
+            char al[8];
+            for (int j = 0; j < W; ++j) al[j] = alive[(size_t)r * W + j] != 0;
+            beam_whole(c, r, sc + (size_t)r * W, al, c->nbest[r]);
+            c->best_recs[r] = c->nbest[r].empty() ? c->committed_recs[r] : c->nbest[r][0].recs;
+        }
         c->neg_logp[r] = -score;
         c->align[r] = 0.0;                                     // alignment_score is a greedy-loop metric
     }
@@ -429,8 +436,13 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
 // host side of a predictor reset in beam mode: the best hypothesis so far is frozen, the beam restarts
 void beam_host_reset(lasr_ctx* c, int slot, bool forget) {
     if (c->W <= 1) return;
-    if (forget) { c->committed[slot].clear(); c->committed_score[slot] = 0.0; c->best_full[slot].clear(); }
-    else { c->committed[slot] = c->best_full[slot]; c->committed_score[slot] = -c->neg_logp[slot]; }
+    if (forget) {
+        c->committed[slot].clear(); c->committed_score[slot] = 0.0; c->best_full[slot].clear();
+        c->committed_recs[slot].clear(); c->best_recs[slot].clear(); c->nbest[slot].clear();
+    } else {
+        c->committed[slot] = c->best_full[slot]; c->committed_score[slot] = -c->neg_logp[slot];
+        c->committed_recs[slot] = c->best_recs[slot];      // (parallel to committed while records are on, empty while they are off)
+    }
     bh_reset(c->bh[slot], c->W);
 }
 

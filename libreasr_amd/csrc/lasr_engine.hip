@@ -72,6 +72,8 @@ void lasr_destroy(lasr_ctx* c) {
     for (auto& e : c->tr_ev) (void)hipEventDestroy(e);
     if (c->tr_base) (void)hipEventDestroy(c->tr_base);
     if (c->trellis_host) (void)hipHostFree(c->trellis_host);
+    if (c->rec_host) (void)hipHostFree(c->rec_host);
+    if (c->b_rec_ring_host) (void)hipHostFree(c->b_rec_ring_host);
     if (c->push_stage_host) (void)hipHostFree(c->push_stage_host);
     if (c->stream_copy) { (void)hipStreamSynchronize(c->stream_copy); (void)hipStreamDestroy(c->stream_copy); }
     for (auto& e : c->push_copied)
@@ -288,6 +290,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         for (auto& b : c->bh) bh_reset(b, c->W);
         c->committed.assign(M, {}); c->committed_score.assign(M, 0.0); c->best_full.assign(M, {});
         c->b_frames_done.assign(M, 0); c->b_results.assign(M, {});
+        c->nbest.assign(M, {}); c->committed_recs.assign(M, {}); c->best_recs.assign(M, {}); c->b_frame_off.assign(M, 0);
         {   // continuous beam loop: the rounds' records, frame marks and step-end scores in pinned host memory (zero-copy stores)
             const size_t n_tre = (size_t)lasr_ctx::TRING * Md, n_fd = (size_t)lasr_ctx::TRING * M;
             const size_t n_es = (size_t)M * lasr_ctx::ENDSLOTS * c->W, n_ea = (size_t)M * lasr_ctx::ENDSLOTS;
@@ -535,6 +538,7 @@ static int reset_impl(lasr_ctx* c, const int* slots, int n, int what) {
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
         if (what & 8) { c->n_chunks[slot] = 0; c->n_pend[slot] = 0; c->queue[slot].clear(); c->rqueue[slot].clear(); c->neg_logp[slot] = 0.0; }
+        if ((what & 8) && c->W > 1) c->nbest[slot].clear();
         if (what & 2) beam_host_reset(c, slot, (what & 8) != 0);
     }
     if (what & 7) {
@@ -581,6 +585,7 @@ int lasr_stream_close(lasr_ctx* c, int slot) {
             return fail(c, LASR_ESTATE, "slot %d has a submitted step in flight: call lasr_step_wait first", slot);
     c->open_[slot] = 0;
     c->queue[slot].clear(); c->rqueue[slot].clear();
+    if (c->W > 1) c->nbest[slot].clear();
     return LASR_OK;
 }
 
@@ -1130,6 +1135,8 @@ static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fuse
     bool kicked = false;
     {
         std::lock_guard<std::mutex> lk(c->mu);
+        if (c->W > 1)       // beam_replay (pump thread, under c->mu) maps the records' global frames to the slot's count with it
+            for (int r : p.rows) c->b_frame_off[r] = p.frame_off[r];
         c->pending.push_back(std::move(p));
         if (c->pump_on) { c->kick.fetch_add(1, std::memory_order_release); kicked = true; }     // (under c->mu: see pump_kick)
     }
@@ -1285,6 +1292,7 @@ static void cont_states(lasr_ctx* c, DecState& s, BeamState& bs) {
         bs.cont = 1; bs.tring = lasr_ctx::TRING; bs.frame_done = c->b_fdone_dev; bs.iter_ctr = c->c_iter; bs.done_blocks = c->c_done;
         bs.host_cur = c->c_hcur_dev; bs.step_T = c->d.n_buffer; bs.end_slots = lasr_ctx::ENDSLOTS;
         bs.end_score = c->b_endsc_dev; bs.end_alive = c->b_endal_dev;
+        bs.rec = c->beam_rec_on ? c->b_rec_ring_dev : nullptr;
     }
 }
 
@@ -1485,15 +1493,17 @@ static int cont_launch_group(lasr_ctx* c, int G, bool from_pump = false) {
 // finished a model step in a round gets that step's result (best alive slot by the scores the kernel stored for the step)
 static void beam_replay(lasr_ctx* c) {
     const int W = c->W, Md = c->Md, M = c->M, Tm = c->d.n_buffer;
+    const bool recs = c->beam_rec_on;
     for (long long it = c->b_rounds_replayed; it < c->cont_iters; ++it) {
         const int slot = (int)(it % lasr_ctx::TRING);
         const int* tre = c->b_tre_host + (size_t)slot * Md;
+        const BeamRec* rr = recs ? c->b_rec_ring_host + (size_t)slot * Md : nullptr;
         const int* fd = c->b_fdone_host + (size_t)slot * M;
         for (int q = 0; q < c->d.max_streams; ++q) {
             const int* e = tre + (size_t)q * W;
             if (e[0] == -1) continue;                          // stream idle in this round
             auto& H = c->bh[q];
-            bh_apply(H, e, W);
+            bh_apply(H, e, W, rr ? rr + (size_t)q * W : nullptr, -c->b_frame_off[q]);   // (global frame cursor -> the slot's own count)
             if (!fd[q]) continue;
             const long long frames = ++c->b_frames_done[q];
             if (frames % Tm) continue;
@@ -1507,6 +1517,12 @@ static void beam_replay(lasr_ctx* c) {
             r.tokens = c->committed[q];
             r.score = c->committed_score[q];
             if (best >= 0) { bh_tokens(H, H.cur[best], r.tokens); r.score += sc[best]; }
+            if (recs) {
+                char al[8];
+                for (int j = 0; j < W; ++j) al[j] = (am >> j) & 1;
+                beam_whole(c, q, sc, al, r.nbest);
+                if (r.nbest.empty()) r.recs = c->committed_recs[q];      // (no slot alive: the frozen prefix alone)
+            }
             c->b_results[q].push_back(std::move(r));
         }
     }
@@ -1702,6 +1718,11 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
             if (c->b_results[r].empty()) return fail(c, LASR_EHIP, "beam: no result for slot %d although its step is decoded", r);
             lasr_ctx::BeamResult& br = c->b_results[r].front();
             c->queue[r] = br.tokens; c->best_full[r] = br.tokens;
+            if (c->beam_rec_on) {
+                c->nbest[r] = std::move(br.nbest);
+                if (c->nbest[r].empty()) c->best_recs[r] = std::move(br.recs);
+                else c->best_recs[r] = c->nbest[r][0].recs;      // hypothesis 0's records outlive the fetch: a predictor reset freezes them
+            }
             c->neg_logp[r] = -br.score; c->align[r] = 0.0;
             c->b_results[r].pop_front();
         }
@@ -1841,6 +1862,7 @@ int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, doub
     if (!q.empty()) memcpy(tokens, q.data(), sizeof(int32_t) * q.size());
     *n_new = (int)q.size();
     q.clear(); c->rqueue[slot].clear();       // (the records of tokens handed out without them are dropped)
+    if (c->W > 1) c->nbest[slot].clear();     // (and so is the rest of the beam: lasr_fetch_nbest consumes the same result)
     if (neg_logp) *neg_logp = c->neg_logp[slot];
     if (align) *align = c->align[slot];
     return LASR_OK;
@@ -1858,6 +1880,7 @@ int lasr_fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int c
         if (!q.empty()) memcpy(tokens + (size_t)i * cap, q.data(), sizeof(int32_t) * q.size());
         n_new[i] = (int)q.size();
         q.clear(); c->rqueue[slots[i]].clear();
+        if (c->W > 1) c->nbest[slots[i]].clear();
     }
     return LASR_OK;
 }
@@ -1937,6 +1960,92 @@ int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* token
         n_new[i] = (int)q.size();
         q.clear(); rq.clear();
     }
+    return LASR_OK;
+}
+
+// ---------------------------------------------------------------------------- beam: per-token records and the whole beam
+// k_beam_select_rw<WT, true> stores, beside the trellis word of every slot it extends by a non-blank token, the frame cursor and the
+// f32 term it added to the parent's score (BeamState::rec; null = off, the default: the <WT, false> instantiation).  Toggling
+// changes which kernel the decode launches run and what the host keeps per node, so the engine must be idle, and the cached groups
+// of the pipelined protocol (BeamState is captured by value) are dropped.
+int lasr_set_beam_records(lasr_ctx* c, int on) {
+    if (!c) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "beam records serve beam search (beam > 1); greedy decode has lasr_set_alignments");
+    const bool want = on != 0;
+    if (want == c->beam_rec_on) return LASR_OK;       // (nothing to switch: also fine while steps are in flight)
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    for (int s = 0; s < c->M; ++s)
+        if (!c->queue[s].empty() || !c->nbest[s].empty())
+            return fail(c, LASR_ESTATE, "slot %d holds a result that was not fetched: fetch it before the switch", s);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    {
+        std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
+        for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
+        c->graphs.clear();
+        for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
+        c->cgraphs.clear();
+    }
+    if (want && !c->b_rec_ring_host) {
+        const size_t n = (size_t)lasr_ctx::TRING * c->Md;
+        HIPCHK(c, hipHostMalloc((void**)&c->b_rec_ring_host, sizeof(BeamRec) * n));
+        memset(c->b_rec_ring_host, 0, sizeof(BeamRec) * n);
+        void* dp = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&dp, c->b_rec_ring_host, 0));
+        c->b_rec_ring_dev = (BeamRec*)dp;
+    }
+    if (want) RC(alloc_beam_recs(c));                 // sized for the trellis as it is now (it may have grown while the switch was off)
+    else free_beam_recs(c);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->beam_rec_on = want;
+    // the host's trees and frozen prefixes keep frame / logp parallel to the tokens exactly while records are on: tokens decoded
+    // before a switch-on have no record (frame -1, log p 0); a switch-off drops them all
+    for (int s = 0; s < c->M; ++s) {
+        auto& B = c->bh[s];
+        if (want) {
+            B.frame.assign(B.par.size(), -1); B.logp.assign(B.par.size(), 0.f);
+            c->committed_recs[s].assign(c->committed[s].size(), BeamRec{-1, 0.f});
+            c->best_recs[s].assign(c->best_full[s].size(), BeamRec{-1, 0.f});
+        } else {
+            B.frame.clear(); B.logp.clear();
+            c->committed_recs[s].clear(); c->best_recs[s].clear();
+        }
+    }
+    return LASR_OK;
+}
+
+int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_tokens,
+                     double* scores, int* n_hyps) {
+    if (!c || !n_hyps) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_fetch_nbest serves beam search (beam > 1)");
+    if (!c->beam_rec_on) return fail(c, LASR_ESTATE, "beam records are off: call lasr_set_beam_records first");
+    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
+    if (max_hyps < 0 || cap < 0 || (max_hyps > 0 && (!tokens || !n_tokens || !scores))) return fail(c, LASR_EINVAL, "bad argument");
+    auto& nb = c->nbest[slot];
+    const int take = std::min(max_hyps, (int)nb.size());
+    bool full = false;
+    for (int i = 0; i < take; ++i) full |= (int)nb[i].tokens.size() > cap;
+    if (full) {
+        int need = 0;
+        for (int i = 0; i < take; ++i) { n_tokens[i] = (int)nb[i].tokens.size(); need = std::max(need, n_tokens[i]); }
+        *n_hyps = (int)nb.size();
+        return fail(c, LASR_EFULL, "token buffers too small: need %d per hypothesis", need);
+    }
+    for (int i = 0; i < take; ++i) {
+        const auto& h = nb[i];
+        const size_t o = (size_t)i * cap;
+        for (size_t j = 0; j < h.tokens.size(); ++j) {
+            tokens[o + j] = h.tokens[j];
+            if (frames) frames[o + j] = h.recs[j].frame;
+            if (logps) logps[o + j] = h.recs[j].logp;
+        }
+        n_tokens[i] = (int)h.tokens.size();
+        scores[i] = h.score;
+    }
+    *n_hyps = (int)nb.size();
+    nb.clear(); c->queue[slot].clear(); c->rqueue[slot].clear();
     return LASR_OK;
 }
 

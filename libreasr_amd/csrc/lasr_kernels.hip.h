@@ -26,6 +26,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "lasr_beamhist.hip.h"      // BeamRec (standard C++ only)
+
 namespace lasr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -931,6 +933,10 @@ struct BeamState {
     // also owns the host publication of the round (lm_on: k_beam_select does not publish to the host)
     int lm_on;
     int* done2;          // [64] second arrival counter (k_beam_fuse)
+    // per-token records (lasr_set_beam_records): indexed like trellis -- round slot, row.  A slot that was extended by a
+    // non-blank token gets (frame cursor at entry, the joint's log p of the extension: the f32 term that went into its score);
+    // every other entry is stale.  Null = off (k_beam_select_rw<WT, false> never looks).
+    BeamRec* rec;        // [n_iter_slots | tring][Md]
 };
 
 // k_beam_select with ONE WAVE PER HYPOTHESIS ROW (V <= 2048, the 512-thread form's arithmetic): wave b keeps row b's logits in
@@ -941,7 +947,9 @@ struct BeamState {
 // "virtual threads" lane + 64 vw (vw = 0..7) of the old layout, the exp-sums are taken per virtual wave with the same butterfly
 // and added in the same order, and the selection itself is a total order (score descending, ordinal ascending) -- any correct
 // algorithm returns the same list.  (A row's candidates in the global top-W are its best by log p: the score offset is per row.)
-template <int WT>
+// REC (records on): a third WT x WT table carries every candidate's f32 term to wave 0 beside its score and ordinal; the slots wave
+// 0 extends store (t, term) into s.rec.  REC = false is the kernel as it was.
+template <int WT, bool REC>
 __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restrict__ logits, BeamState s, int iter_slot) {
     constexpr int VW = 8, KEEP = 4, NTV = 512;      // virtual waves / slots per virtual thread / virtual threads (the old layout)
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -991,6 +999,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     }
     __shared__ double cand_sc[WT][WT];
     __shared__ int cand_ord[WT][WT];
+    __shared__ float cand_lp[REC ? WT : 1][REC ? WT : 1];      // (read only where cand_sc holds a candidate of the same round)
     // (the table starts empty: a wave that looks at it while others are still writing -- the pruning below -- sees "no candidate")
     if (tid < WT * WT) { cand_sc[tid / WT][tid % WT] = -INFINITY; cand_ord[tid / WT][tid % WT] = 0x7fffffff; }
     __syncthreads();
@@ -1077,7 +1086,10 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
             wave_argmax_f32(best, arg);
             if (!(best > -INFINITY)) break;           // the row's candidates are exhausted (wave-uniform)
             const double myv = scb + (double)best;
-            if (lane == 0) { cand_sc[b][j] = myv; cand_ord[b][j] = b * (V + 1) + 1 + arg; }
+            if (lane == 0) {
+                if constexpr (REC) cand_lp[b][j] = best;        // (before the score: a reader that sees the candidate finds its term; wave 0 reads behind the barrier anyway)
+                cand_sc[b][j] = myv; cand_ord[b][j] = b * (V + 1) + 1 + arg;
+            }
             {
                 // Pruning: once W candidates of ANY row are strictly better than this one, neither it nor anything this row could
                 // still offer is in the global top-W -- stop.  The other waves' entries are read while they write them: an entry is
@@ -1114,6 +1126,8 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     double my_sc = -INFINITY;
     int my_ord = 0x7fffffff;
     if (lane < WT * WT) { my_sc = cand_sc[lane / WT][lane % WT]; my_ord = cand_ord[lane / WT][lane % WT]; }
+    int my_lp = 0, slp = 0;                            // (REC) bit patterns of the candidate's / the selected candidate's f32 term
+    if constexpr (REC) { if (lane < WT * WT && my_sc > -INFINITY) my_lp = __float_as_int(cand_lp[lane / WT][lane % WT]); }
     const bool valid = my_sc > -INFINITY;
     int rank = 0;
     {
@@ -1135,6 +1149,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
         const double v = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_sc), src), __builtin_amdgcn_readlane(__double2loint(my_sc), src));
         const int o = __builtin_amdgcn_readlane(my_ord, src);
         if (lane == jj) { sel = v; sord = o; }
+        if constexpr (REC) { const int l = __builtin_amdgcn_readlane(my_lp, src); if (lane == jj) slp = l; }
     }
     if (dbg) s.dbg[3] = wall_clock64();
     const int round = s.iters[q] + 1;
@@ -1155,7 +1170,11 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
             }
             s.emit[r] = em;
             tre[lane] = (pb << 16) | (em ? k : 0);
+            if (REC && em) s.rec[(size_t)(s.cont ? iter_no % s.tring : iter_slot) * s.Md + r] = BeamRec{t, __int_as_float(slp)};
         }
+        // continuous mode: lane 0 alone fences and arrives in publish(); every lane that stored a record orders its own store
+        // towards the host here, in front of that arrival (no second flag, no new release)
+        if (REC && s.cont && s.host_flag && !s.lm_on) __threadfence_system();
     }
     const bool all_b = __ballot(slot && !inb) == 0ull;
     const int am = (int)(__ballot(live) & ((1ull << W) - 1ull));

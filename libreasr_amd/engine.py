@@ -323,6 +323,29 @@ class Engine:
                                                    lp.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p)))
         return [(tok[i, :k].tolist(), fr[i, :k].copy(), lp[i, :k].copy()) for i, k in enumerate(cnt.tolist())]
 
+    # ------------------------------------------------------------------ beam: per-token records and the whole beam
+    def set_beam_records(self, on=True):
+        """Whole-beam results with per-token emission frame and log p from beam decode (lasr_set_beam_records): off by default; to
+        switch, the engine must be idle (no submitted step uncollected, no result unfetched).  beam = 1: LasrError (LASR_EINVAL)."""
+        self._chk(self.lib.lasr_set_beam_records(self.ctx, 1 if on else 0))
+
+    def fetch_nbest(self, slot, max_hyps=None, cap=65536):
+        """fetch(slot) for the whole beam -> [(tokens, frames, logps, score)], best first (score descending, then hypothesis slot
+        ascending; no merging): up to max_hyps (default: the beam width) of the hypotheses alive after the last model step.
+        frames / logps as in fetch_aligned; score = sum of log p of every decision; entry 0 is what fetch would have returned."""
+        k = self.beam if max_hyps is None else int(max_hyps)
+        tok = np.empty((max(k, 1), cap), dtype=np.int32)
+        fr = np.empty((max(k, 1), cap), dtype=np.int32)
+        lp = np.empty((max(k, 1), cap), dtype=np.float32)
+        cnt = np.zeros(max(k, 1), dtype=np.int32)
+        sc = np.zeros(max(k, 1), dtype=np.float64)
+        nh = C.c_int(0)
+        self._chk(self.lib.lasr_fetch_nbest(self.ctx, int(slot), k, tok.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p),
+                                            lp.ctypes.data_as(C.c_void_p), cap, cnt.ctypes.data_as(C.c_void_p),
+                                            sc.ctypes.data_as(C.c_void_p), C.byref(nh)))
+        return [(tok[i, :cnt[i]].tolist(), fr[i, :cnt[i]].copy(), lp[i, :cnt[i]].copy(), float(sc[i]))
+                for i in range(min(k, nh.value))]
+
     # ------------------------------------------------------------------ offline
     def transcribe_pcm(self, slots, pcm_list):
         """pcm_list: list of 1-D float32 arrays/tensors (one utterance per slot)."""
