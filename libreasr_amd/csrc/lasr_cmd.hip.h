@@ -122,10 +122,7 @@ int alloc_beam_recs(lasr_ctx* c) {
 int ensure_T(lasr_ctx* c, int T) {
     if (T <= c->Tcap) return LASR_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);   // captured pointers become stale
-    c->graphs.clear();
-    for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
-    c->cgraphs.clear();
+    drop_decode_graphs(c);                                              // captured pointers become stale
     for (auto& kv : c->mgraphs) (void)hipGraphExecDestroy(kv.second);
     c->mgraphs.clear();
     const int M = c->M, H = c->d.hidden, F = c->d.feat, J = c->d.joint;

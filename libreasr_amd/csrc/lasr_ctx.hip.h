@@ -3,6 +3,8 @@
 #pragma once
 #include <dlfcn.h>
 
+#include "lasr_results.hip.h"
+
 constexpr int NW = 8;          // waves per GEMM workgroup (K split)
 constexpr int NCMD = 64;       // ring of host->device command blocks
 constexpr int MTA = 4;         // m-tiles per workgroup in the "A" tiling (64 rows)
@@ -60,9 +62,8 @@ struct lasr_ctx {
     // beam search: c, BN(h) and pp ping-pong like h (every slot may be re-parented each round): pred_c / pred_y / pp are indexed
     // by parity and follow pred_par (par_rd / par_wr below); index 1 exists with a beam only
     double* b_score = nullptr; int *b_alive = nullptr, *b_inB = nullptr, *b_parent = nullptr, *b_trellis = nullptr;
-    // host: token history of every hypothesis slot as a shared-prefix tree per stream (lasr_beamhist.hip.h)
-    using BeamHost = ::BeamHost;
-    std::vector<BeamHost> bh;
+    // host: per stream, the hypothesis tree, the frozen prefix, the current best and the uncollected step results (lasr_results.hip.h)
+    std::vector<BeamSlot> beams;
     // continuous beam loop (lasr_step_submit / lasr_step_wait with beam > 1): pinned rings written by k_beam_select
     static constexpr int TRING = 128;
     int *b_tre_host = nullptr, *b_tre_dev = nullptr;         // [TRING][Md] records of a round
@@ -72,22 +73,14 @@ struct lasr_ctx {
     long long b_rounds_replayed = 0;
     std::vector<long long> b_frames_done;                    // per stream: frames the host has seen finished
     // per-token records + whole-beam results (lasr_set_beam_records / lasr_fetch_nbest).  Off (the default): no
-    // allocation, BeamState::rec null, every vector below stays empty.  On: a finished model step's result is every alive
-    // hypothesis, best first (score descending, then slot ascending), as MATERIALISED lists (committed prefix + path of the tree).
-    struct BeamHyp { std::vector<int32_t> tokens; std::vector<BeamRec> recs; double score; };
+    // allocation, BeamState::rec null, every record vector of `beams` / `results` stays empty.  On: a finished model step's result is
+    // every alive hypothesis, best first (score descending, then slot ascending), as MATERIALISED lists (BeamSlot::build).
     bool beam_rec_on = false;
     BeamRec* b_rec = nullptr;                                // device [n_iter_slots][Md], beside b_trellis (synchronous / offline steps)
     BeamRec* rec_host = nullptr;                             // pinned: its copy, once per step
     int rec_slots = 0;                                       // rounds both were sized for (== n_iter_slots while the switch is on, else 0)
     BeamRec *b_rec_ring_host = nullptr, *b_rec_ring_dev = nullptr;   // pinned [TRING][Md], beside b_tre_host (allocated at the first switch-on)
     std::vector<long long> b_frame_off;                      // per stream: global frame cursor minus the slot's own count (set at submit, under mu)
-    std::vector<std::vector<BeamHyp>> nbest;                 // per slot: the beam of the last collected model step, until fetched
-    std::vector<std::vector<BeamRec>> committed_recs, best_recs;     // parallel to committed / best_full
-    struct BeamResult { std::vector<int32_t> tokens; double score; std::vector<BeamHyp> nbest; std::vector<BeamRec> recs; };   // recs: only when nbest is empty
-    std::vector<std::deque<BeamResult>> b_results;           // per stream: finished model steps not yet collected
-    std::vector<std::vector<int32_t>> committed;          // host: best hypothesis at the last predictor reset(s)
-    std::vector<double> committed_score;
-    std::vector<std::vector<int32_t>> best_full;          // host: committed + current best hypothesis
     int* trellis_host = nullptr; size_t trellis_host_ints = 0;
     int enc_par = 0;
     int pred_par = 0;               // predictor h ping-pong parity (row-major [M][H] buffers)
@@ -304,13 +297,8 @@ struct lasr_ctx {
     // host mirrors
     std::vector<char> open_;
     std::vector<int> n_chunks, n_pend;
-    std::vector<std::vector<int32_t>> queue;
-    std::vector<double> neg_logp, align;
-    // per-token alignment records (lasr_set_alignments; greedy decode).  While on, rqueue[slot] runs parallel to queue[slot]: every
-    // place that fills, clears or pops the one does the same to the other.
-    struct TokRec { int32_t frame; float logp; };
-    bool align_on = false;
-    std::vector<std::vector<TokRec>> rqueue;
+    std::vector<SlotResult> results;      // per slot: what the fetch calls hand out (lasr_results.hip.h)
+    bool align_on = false;                // per-token alignment records (lasr_set_alignments; greedy decode)
     std::vector<long long> slot_frames;   // encoder frames the slot has consumed since lasr_stream_open (either protocol)
     int* align_host = nullptr;            // pinned [frames M x TOKRING][log p M x TOKRING]: k_select's record rings (allocated on first use)
     int* c_frame_ring = nullptr; float* c_logp_ring = nullptr;      // device views of the two halves
@@ -438,6 +426,14 @@ int dalloc0(lasr_ctx* c, T** p, size_t n) {      // dalloc + zero fill (after th
     RC(dalloc(c, p, n));
     HIPCHK(c, hipMemset(*p, 0, n * sizeof(T)));
     return LASR_OK;
+}
+// the cached decode groups of both protocols (they bake in DecState / BeamState and buffer addresses).  The pump thread looks them up
+// under c->mu: whoever may race with it holds that lock.
+void drop_decode_graphs(lasr_ctx* c) {
+    for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
+    c->graphs.clear();
+    for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
+    c->cgraphs.clear();
 }
 void dfree(lasr_ctx* c, void* p) {
     if (!p) return;

@@ -186,26 +186,6 @@ void run_encoder(lasr_ctx* c, int T_max) {
     launch_linear<false, 3>(c, J / 16, T_max * c->MT, g, H, ea);
 }
 
-// ---- host side of the beam: hypotheses as a shared-prefix tree per stream: lasr_beamhist.hip.h (bh_reset / bh_tokens / bh_records /
-// bh_apply).  Records on: the whole beam of stream r at the end of a model step -- every alive slot, score descending, ties by slot
-// ascending (the order in which the `best` loops pick their winner: hypothesis 0 is lasr_fetch's), each the committed prefix
-// followed by the slot's path; scores include committed_score.
-void beam_whole(lasr_ctx* c, int r, const double* sc, const char* alive, std::vector<lasr_ctx::BeamHyp>& out) {
-    const int W = c->W;
-    int ord[8], n = 0;
-    for (int j = 0; j < W; ++j)
-        if (alive[j]) ord[n++] = j;
-    std::stable_sort(ord, ord + n, [&](int a, int b) { return sc[a] > sc[b]; });
-    const auto& H = c->bh[r];
-    out.clear(); out.resize(n);
-    for (int i = 0; i < n; ++i) {
-        auto& h = out[i];
-        h.tokens = c->committed[r]; h.recs = c->committed_recs[r];
-        bh_tokens(H, H.cur[ord[i]], h.tokens); bh_records(H, H.cur[ord[i]], h.recs);
-        h.score = c->committed_score[r] + sc[ord[i]];
-    }
-}
-
 // Greedy decode of the current step (T_row_dev, pe ready).  Blocks until done; fills host queues.
 int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::vector<int>& rows);
 
@@ -328,19 +308,18 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     }
     for (int r : rows) {
         const int n = std::min(ntok[r], s.tok_cap);
-        for (int q = 0; q < n; ++q) c->queue[r].push_back(toks[(size_t)r * s.tok_cap + q]);
-        if (recs) {
-            // the kernel's frame cursor starts at 0 in every step: + the frames the slot consumed before this call (offline: the
-            // utterance starts the count)
-            const long long base = offline ? 0 : c->slot_frames[r];
-            for (int q = 0; q < n; ++q)
-                c->rqueue[r].push_back({(int32_t)(base + frames[(size_t)r * s.tok_cap + q]), logps[(size_t)r * s.tok_cap + q]});
-        }
-        c->slot_frames[r] = (offline ? 0 : c->slot_frames[r]) + c->hc.T_row[r];
+        SlotResult& out = c->results[r];
+        const size_t at = (size_t)r * s.tok_cap;
+        // the kernel's frame cursor starts at 0 in every step: + the frames the slot consumed before this call (offline: the
+        // utterance starts the count)
+        const long long base = offline ? 0 : c->slot_frames[r];
+        if (!recs) for (int q = 0; q < n; ++q) out.append(toks[at + q]);
+        else for (int q = 0; q < n; ++q) out.append(toks[at + q], {(int32_t)(base + frames[at + q]), logps[at + q]});
+        c->slot_frames[r] = base + c->hc.T_row[r];
         if (offline) {
-            c->neg_logp[r] = -logp[r];
+            out.neg_logp = -logp[r];
             // alignment_score = (sum(iters) - #frames with 1 iter) / (sum(iters) + 1e-4)  (models.py:447-453)
-            c->align[r] = ((double)sum_iters[r] - (double)n_ones[r]) / ((double)sum_iters[r] + 1e-4);
+            out.align = ((double)sum_iters[r] - (double)n_ones[r]) / ((double)sum_iters[r] + 1e-4);
         }
     }
     return LASR_OK;
@@ -403,47 +382,28 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
     if (recs) HIPCHK(c, hipMemcpyAsync(c->rec_host, c->b_rec, sizeof(BeamRec) * (size_t)iter * Md, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int r : rows) {
-        auto& H = c->bh[r];
+        BeamSlot& B = c->beams[r];
         // the kernel's frame cursor starts at 0 in every step: + the frames the slot consumed before this call (offline: the
         // utterance starts the count), as in run_decode
         const long long base = offline ? 0 : c->slot_frames[r];
         for (int it = 0; it < iter; ++it) {
             const int* e = tre + (size_t)it * Md + (size_t)r * W;
             if (e[0] == -1) continue;                          // stream idle in this round
-            bh_apply(H, e, W, recs ? c->rec_host + (size_t)it * Md + (size_t)r * W : nullptr, base);
+            bh_apply(B.tree, e, W, recs ? c->rec_host + (size_t)it * Md + (size_t)r * W : nullptr, base);
         }
         c->slot_frames[r] = base + c->hc.T_row[r];
-        int best = -1;
-        for (int j = 0; j < W; ++j)
-            if (alive[(size_t)r * W + j] && (best < 0 || sc[(size_t)r * W + j] > sc[(size_t)r * W + best])) best = j;
-        auto& q = c->best_full[r];
-        q = c->committed[r];                                   // what earlier predictor resets froze
-        double score = c->committed_score[r];
-        if (best >= 0) { bh_tokens(H, H.cur[best], q); score += sc[(size_t)r * W + best]; }
-        c->queue[r] = q;                                       // beam mode: lasr_fetch hands out the whole best hypothesis
-        if (recs) {
-            char al[8];
-            for (int j = 0; j < W; ++j) al[j] = alive[(size_t)r * W + j] != 0;
-            beam_whole(c, r, sc + (size_t)r * W, al, c->nbest[r]);
-            c->best_recs[r] = c->nbest[r].empty() ? c->committed_recs[r] : c->nbest[r][0].recs;
-        }
-        c->neg_logp[r] = -score;
-        c->align[r] = 0.0;                                     // alignment_score is a greedy-loop metric
+        unsigned am = 0;
+        for (int j = 0; j < W; ++j) am |= (alive[(size_t)r * W + j] != 0) << j;
+        B.deliver(B.build(sc + (size_t)r * W, am, recs), c->results[r]);      // beam mode: lasr_fetch hands out the whole best hypothesis
     }
     return LASR_OK;
 }
 
-// host side of a predictor reset in beam mode: the best hypothesis so far is frozen, the beam restarts
+// host side of a predictor reset in beam mode: the best hypothesis so far is frozen (or, with the transcript, forgotten)
 void beam_host_reset(lasr_ctx* c, int slot, bool forget) {
     if (c->W <= 1) return;
-    if (forget) {
-        c->committed[slot].clear(); c->committed_score[slot] = 0.0; c->best_full[slot].clear();
-        c->committed_recs[slot].clear(); c->best_recs[slot].clear(); c->nbest[slot].clear();
-    } else {
-        c->committed[slot] = c->best_full[slot]; c->committed_score[slot] = -c->neg_logp[slot];
-        c->committed_recs[slot] = c->best_recs[slot];      // (parallel to committed while records are on, empty while they are off)
-    }
-    bh_reset(c->bh[slot], c->W);
+    if (forget) c->beams[slot].forget();
+    else c->beams[slot].freeze(-c->results[slot].neg_logp);
 }
 
 void rec(lasr_ctx* c, int i) {

@@ -94,8 +94,7 @@ void lasr_destroy(lasr_ctx* c) {
     if (c->cp_ok)
         for (auto& p : c->cp_ev)
             for (auto& e : p) (void)hipEventDestroy(e);
-    for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
-    for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
+    drop_decode_graphs(c);
     for (auto& kv : c->mgraphs) (void)hipGraphExecDestroy(kv.second);
     if (c->stream_cap) (void)hipStreamDestroy(c->stream_cap);
     if (c->stream_dec) { (void)hipStreamSynchronize(c->stream_dec); (void)hipStreamDestroy(c->stream_dec); }
@@ -286,11 +285,9 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         }
         RC(dalloc0(c, &c->pp[1], (size_t)Md * J));
         RC(dalloc0(c, &c->b_score, Md)); RC(dalloc0(c, &c->b_alive, Md)); RC(dalloc0(c, &c->b_inB, Md)); RC(dalloc0(c, &c->b_parent, Md));
-        c->bh.assign(M, lasr_ctx::BeamHost{});
-        for (auto& b : c->bh) bh_reset(b, c->W);
-        c->committed.assign(M, {}); c->committed_score.assign(M, 0.0); c->best_full.assign(M, {});
-        c->b_frames_done.assign(M, 0); c->b_results.assign(M, {});
-        c->nbest.assign(M, {}); c->committed_recs.assign(M, {}); c->best_recs.assign(M, {}); c->b_frame_off.assign(M, 0);
+        c->beams.assign(M, BeamSlot{});
+        for (auto& b : c->beams) bh_reset(b.tree, c->W);
+        c->b_frames_done.assign(M, 0); c->b_frame_off.assign(M, 0);
         {   // continuous beam loop: the rounds' records, frame marks and step-end scores in pinned host memory (zero-copy stores)
             const size_t n_tre = (size_t)lasr_ctx::TRING * Md, n_fd = (size_t)lasr_ctx::TRING * M;
             const size_t n_es = (size_t)M * lasr_ctx::ENDSLOTS * c->W, n_ea = (size_t)M * lasr_ctx::ENDSLOTS;
@@ -436,8 +433,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
     }
 
     c->open_.assign(M, 0); c->n_chunks.assign(M, 0); c->n_pend.assign(M, 0);
-    c->queue.assign(M, {}); c->neg_logp.assign(M, 0.0); c->align.assign(M, 0.0);
-    c->rqueue.assign(M, {}); c->slot_frames.assign(M, 0);
+    c->results.assign(M, SlotResult{}); c->slot_frames.assign(M, 0);
     c->ev_ok = true;
     for (auto& e : c->ev)
         if (hipEventCreate(&e) != hipSuccess) c->ev_ok = false;
@@ -537,8 +533,7 @@ static int reset_impl(lasr_ctx* c, const int* slots, int n, int what) {
     if (what & 8) RC(flush_lazy(c));         // (the PCM ring of these slots starts over)
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
-        if (what & 8) { c->n_chunks[slot] = 0; c->n_pend[slot] = 0; c->queue[slot].clear(); c->rqueue[slot].clear(); c->neg_logp[slot] = 0.0; }
-        if ((what & 8) && c->W > 1) c->nbest[slot].clear();
+        if (what & 8) { c->n_chunks[slot] = 0; c->n_pend[slot] = 0; c->results[slot].clear(); c->results[slot].neg_logp = 0.0; }
         if (what & 2) beam_host_reset(c, slot, (what & 8) != 0);
     }
     if (what & 7) {
@@ -584,8 +579,7 @@ int lasr_stream_close(lasr_ctx* c, int slot) {
         if (std::find(p.rows.begin(), p.rows.end(), slot) != p.rows.end())
             return fail(c, LASR_ESTATE, "slot %d has a submitted step in flight: call lasr_step_wait first", slot);
     c->open_[slot] = 0;
-    c->queue[slot].clear(); c->rqueue[slot].clear();
-    if (c->W > 1) c->nbest[slot].clear();
+    c->results[slot].clear();
     return LASR_OK;
 }
 
@@ -1162,7 +1156,7 @@ static int32_t ring_token(const lasr_ctx* c, int r, long long q) {
     return h_ring[(size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING)];
 }
 // its alignment record (alignments on): the same ring position of the two record rings, the frame as the slot counts it
-static lasr_ctx::TokRec ring_record(const lasr_ctx* c, const lasr_ctx::PendingStep& P, int r, long long q) {
+static BeamRec ring_record(const lasr_ctx* c, const lasr_ctx::PendingStep& P, int r, long long q) {
     const size_t at = (size_t)r * lasr_ctx::TOKRING + (q % lasr_ctx::TOKRING);
     const float* h_logp = (const float*)(c->align_host + (size_t)c->M * lasr_ctx::TOKRING);
     return {(int32_t)(c->align_host[at] - P.frame_off[r]), h_logp[at]};
@@ -1502,28 +1496,15 @@ static void beam_replay(lasr_ctx* c) {
         for (int q = 0; q < c->d.max_streams; ++q) {
             const int* e = tre + (size_t)q * W;
             if (e[0] == -1) continue;                          // stream idle in this round
-            auto& H = c->bh[q];
-            bh_apply(H, e, W, rr ? rr + (size_t)q * W : nullptr, -c->b_frame_off[q]);   // (global frame cursor -> the slot's own count)
+            BeamSlot& B = c->beams[q];
+            bh_apply(B.tree, e, W, rr ? rr + (size_t)q * W : nullptr, -c->b_frame_off[q]);   // (global frame cursor -> the slot's own count)
             if (!fd[q]) continue;
             const long long frames = ++c->b_frames_done[q];
             if (frames % Tm) continue;
             const int es = (int)((frames / Tm - 1) % lasr_ctx::ENDSLOTS);
             const double* sc = c->b_endsc_host + ((size_t)q * lasr_ctx::ENDSLOTS + es) * W;
             const int am = c->b_endal_host[(size_t)q * lasr_ctx::ENDSLOTS + es];
-            int best = -1;
-            for (int j = 0; j < W; ++j)
-                if (((am >> j) & 1) && (best < 0 || sc[j] > sc[best])) best = j;
-            lasr_ctx::BeamResult r;
-            r.tokens = c->committed[q];
-            r.score = c->committed_score[q];
-            if (best >= 0) { bh_tokens(H, H.cur[best], r.tokens); r.score += sc[best]; }
-            if (recs) {
-                char al[8];
-                for (int j = 0; j < W; ++j) al[j] = (am >> j) & 1;
-                beam_whole(c, q, sc, al, r.nbest);
-                if (r.nbest.empty()) r.recs = c->committed_recs[q];      // (no slot alive: the frozen prefix alone)
-            }
-            c->b_results[q].push_back(std::move(r));
+            B.steps.push_back(B.build(sc, (unsigned)am, recs));
         }
     }
     c->b_rounds_replayed = c->cont_iters;
@@ -1715,23 +1696,17 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     if (c->W > 1) {      // beam: the whole best hypothesis as of this model step (lasr_fetch semantics of beam > 1)
         for (int r : P.rows) {
-            if (c->b_results[r].empty()) return fail(c, LASR_EHIP, "beam: no result for slot %d although its step is decoded", r);
-            lasr_ctx::BeamResult& br = c->b_results[r].front();
-            c->queue[r] = br.tokens; c->best_full[r] = br.tokens;
-            if (c->beam_rec_on) {
-                c->nbest[r] = std::move(br.nbest);
-                if (c->nbest[r].empty()) c->best_recs[r] = std::move(br.recs);
-                else c->best_recs[r] = c->nbest[r][0].recs;      // hypothesis 0's records outlive the fetch: a predictor reset freezes them
-            }
-            c->neg_logp[r] = -br.score; c->align[r] = 0.0;
-            c->b_results[r].pop_front();
+            BeamSlot& B = c->beams[r];
+            if (B.steps.empty()) return fail(c, LASR_EHIP, "beam: no result for slot %d although its step is decoded", r);
+            B.deliver(std::move(B.steps.front()), c->results[r]);
+            B.steps.pop_front();
         }
     } else
     for (int r : P.rows) {
         const long long end = step_end_mark(c, P, r);
-        for (long long q = c->h_fetched[r]; q < end; ++q) c->queue[r].push_back(ring_token(c, r, q));
-        if (c->align_on)
-            for (long long q = c->h_fetched[r]; q < end; ++q) c->rqueue[r].push_back(ring_record(c, P, r, q));
+        SlotResult& out = c->results[r];
+        if (!c->align_on) for (long long q = c->h_fetched[r]; q < end; ++q) out.append(ring_token(c, r, q));
+        else for (long long q = c->h_fetched[r]; q < end; ++q) out.append(ring_token(c, r, q), ring_record(c, P, r, q));
         c->h_fetched[r] = end;
     }
     c->stats.frames = P.Tm;
@@ -1776,8 +1751,7 @@ int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, 
         c->hc.T_row[s] = Tp[i]; c->hc.what[s] = 7; c->hc.row_frames[s] = Tm[i];
         c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
         off += n_samples[i];
-        c->queue[s].clear(); c->rqueue[s].clear();
-        c->neg_logp[s] = 0.0;
+        c->results[s].clear(); c->results[s].neg_logp = 0.0;
         beam_host_reset(c, s, true);
     }
     RC(cmd_commit(c));
@@ -1813,8 +1787,7 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
         const int s = slots[i];
         c->hc.T_row[s] = n_frames[i]; c->hc.what[s] = 7; c->hc.row_feat_off[s] = off;
         off += n_frames[i];
-        c->queue[s].clear(); c->rqueue[s].clear();
-        c->neg_logp[s] = 0.0;
+        c->results[s].clear(); c->results[s].neg_logp = 0.0;
         beam_host_reset(c, s, true);
     }
     RC(cmd_commit(c));
@@ -1851,37 +1824,60 @@ int lasr_step_feats(lasr_ctx* c, const int* slots, int n, const float* feats, in
     return decode_and_collect(c, T, d.max_iters_stream, false, rows);
 }
 
+// The fetch entry points: each validates its own arguments, then hands the slot's result out through one of these two.
+static int open_slot(lasr_ctx* c, int slot) {
+    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
+    return LASR_OK;
+}
+// one slot; have_bufs: every array the caller must supply is there.  Too little room (or no array): the need is reported, nothing
+// is consumed.  Null frames / logps: the records are dropped with the tokens (and so is the rest of a beam: lasr_fetch_nbest
+// consumes the same result)
+static int fetch_one(lasr_ctx* c, int slot, int32_t* tokens, int32_t* frames, float* logps, bool have_bufs, int cap, int* n_new,
+                     double* neg_logp, double* align) {
+    RC(open_slot(c, slot));
+    SlotResult& r = c->results[slot];
+    if (!r.take(have_bufs ? tokens : nullptr, frames, logps, cap, n_new)) return fail(c, LASR_EFULL, "token buffer too small: need %d", *n_new);
+    if (neg_logp) *neg_logp = r.neg_logp;
+    if (align) *align = r.align;
+    return LASR_OK;
+}
+// n slots into [n][cap] arrays: all of them are checked before anything is consumed (an error leaves n_new alone)
+static int fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_new) {
+    for (int i = 0; i < n; ++i) {
+        RC(open_slot(c, slots[i]));
+        const int need = c->results[slots[i]].need();
+        if (need > cap) return fail(c, LASR_EFULL, "token buffer too small: slot %d needs %d", slots[i], need);
+    }
+    for (int i = 0; i < n; ++i) {
+        const size_t o = (size_t)i * cap;
+        (void)c->results[slots[i]].take(tokens + o, frames ? frames + o : nullptr, logps ? logps + o : nullptr, cap, &n_new[i]);   // (fits: checked above)
+    }
+    return LASR_OK;
+}
+
 int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, double* neg_logp, double* align) {
     if (!c || !n_new) return LASR_EINVAL;
-    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
-    auto& q = c->queue[slot];
-    if ((int)q.size() > cap || (!tokens && !q.empty())) {
-        *n_new = (int)q.size();
-        return fail(c, LASR_EFULL, "token buffer too small: need %d", (int)q.size());
-    }
-    if (!q.empty()) memcpy(tokens, q.data(), sizeof(int32_t) * q.size());
-    *n_new = (int)q.size();
-    q.clear(); c->rqueue[slot].clear();       // (the records of tokens handed out without them are dropped)
-    if (c->W > 1) c->nbest[slot].clear();     // (and so is the rest of the beam: lasr_fetch_nbest consumes the same result)
-    if (neg_logp) *neg_logp = c->neg_logp[slot];
-    if (align) *align = c->align[slot];
-    return LASR_OK;
+    return fetch_one(c, slot, tokens, nullptr, nullptr, tokens != nullptr, cap, n_new, neg_logp, align);
 }
 
 int lasr_fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int cap, int* n_new) {
     if (!c || !n_new || (n > 0 && !slots)) return LASR_EINVAL;
-    for (int i = 0; i < n; ++i) {
-        const int slot = slots[i];
-        if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
-        if ((int)c->queue[slot].size() > cap) return fail(c, LASR_EFULL, "token buffer too small: slot %d needs %d", slot, (int)c->queue[slot].size());
-    }
-    for (int i = 0; i < n; ++i) {
-        auto& q = c->queue[slots[i]];
-        if (!q.empty()) memcpy(tokens + (size_t)i * cap, q.data(), sizeof(int32_t) * q.size());
-        n_new[i] = (int)q.size();
-        q.clear(); c->rqueue[slots[i]].clear();
-        if (c->W > 1) c->nbest[slots[i]].clear();
-    }
+    return fetch_many(c, slots, n, tokens, nullptr, nullptr, cap, n_new);
+}
+
+// What both record switches (lasr_set_alignments, lasr_set_beam_records) do first: the engine idle, no slot with an unfetched result
+// (`unfetched`: the refusal's text, with the slot and its token count as arguments), both streams drained, the cached decode groups
+// dropped
+static int toggle_prologue(lasr_ctx* c, const char* unfetched) {
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    for (int s = 0; s < c->M; ++s)
+        if (c->results[s].unfetched()) return fail(c, LASR_ESTATE, unfetched, s, c->results[s].need());
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
+    drop_decode_graphs(c);
     return LASR_OK;
 }
 
@@ -1895,22 +1891,8 @@ int lasr_set_alignments(lasr_ctx* c, int on) {
     if (c->W > 1) return fail(c, LASR_EINVAL, "alignment records serve greedy decode (beam = 1)");
     const bool want = on != 0;
     if (want == c->align_on) return LASR_OK;       // (nothing to switch: also fine while steps are in flight)
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    // tokens decoded before the switch would have no record (on) or lose theirs (off): they are fetched first, so that
-    // queue[slot] and rqueue[slot] are parallel whenever records are on
-    for (int s = 0; s < c->M; ++s)
-        if (!c->queue[s].empty()) return fail(c, LASR_ESTATE, "slot %d has %d unfetched token(s): fetch them before the switch", s, (int)c->queue[s].size());
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
-    {
-        std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
-        for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
-        c->graphs.clear();
-        for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
-        c->cgraphs.clear();
-    }
+    // tokens decoded before the switch would have no record (on) or lose theirs (off): they are fetched first
+    RC(toggle_prologue(c, "slot %d has %d unfetched token(s): fetch them before the switch"));
     if (want && !c->align_host) {
         const size_t n = (size_t)c->M * lasr_ctx::TOKRING;
         HIPCHK(c, hipHostMalloc((void**)&c->align_host, sizeof(int) * 2 * n));
@@ -1929,38 +1911,13 @@ int lasr_fetch_aligned(lasr_ctx* c, int slot, int32_t* tokens, int32_t* frames, 
                        double* align) {
     if (!c || !n_new) return LASR_EINVAL;
     if (!c->align_on) return fail(c, LASR_ESTATE, "alignment records are off: call lasr_set_alignments first");
-    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
-    auto& q = c->queue[slot];
-    auto& rq = c->rqueue[slot];
-    if ((int)q.size() > cap || ((!tokens || !frames || !logps) && !q.empty())) {
-        *n_new = (int)q.size();
-        return fail(c, LASR_EFULL, "token buffer too small: need %d", (int)q.size());
-    }
-    for (size_t i = 0; i < q.size(); ++i) { tokens[i] = q[i]; frames[i] = rq[i].frame; logps[i] = rq[i].logp; }
-    *n_new = (int)q.size();
-    q.clear(); rq.clear();
-    if (neg_logp) *neg_logp = c->neg_logp[slot];
-    if (align) *align = c->align[slot];
-    return LASR_OK;
+    return fetch_one(c, slot, tokens, frames, logps, tokens && frames && logps, cap, n_new, neg_logp, align);
 }
 
 int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_new) {
     if (!c || !n_new || (n > 0 && (!slots || !tokens || !frames || !logps))) return LASR_EINVAL;
     if (!c->align_on) return fail(c, LASR_ESTATE, "alignment records are off: call lasr_set_alignments first");
-    for (int i = 0; i < n; ++i) {
-        const int slot = slots[i];
-        if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
-        if ((int)c->queue[slot].size() > cap) return fail(c, LASR_EFULL, "token buffer too small: slot %d needs %d", slot, (int)c->queue[slot].size());
-    }
-    for (int i = 0; i < n; ++i) {
-        auto& q = c->queue[slots[i]];
-        auto& rq = c->rqueue[slots[i]];
-        const size_t o = (size_t)i * cap;
-        for (size_t j = 0; j < q.size(); ++j) { tokens[o + j] = q[j]; frames[o + j] = rq[j].frame; logps[o + j] = rq[j].logp; }
-        n_new[i] = (int)q.size();
-        q.clear(); rq.clear();
-    }
-    return LASR_OK;
+    return fetch_many(c, slots, n, tokens, frames, logps, cap, n_new);
 }
 
 // ---------------------------------------------------------------------------- beam: per-token records and the whole beam
@@ -1973,21 +1930,7 @@ int lasr_set_beam_records(lasr_ctx* c, int on) {
     if (c->W <= 1) return fail(c, LASR_EINVAL, "beam records serve beam search (beam > 1); greedy decode has lasr_set_alignments");
     const bool want = on != 0;
     if (want == c->beam_rec_on) return LASR_OK;       // (nothing to switch: also fine while steps are in flight)
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    for (int s = 0; s < c->M; ++s)
-        if (!c->queue[s].empty() || !c->nbest[s].empty())
-            return fail(c, LASR_ESTATE, "slot %d holds a result that was not fetched: fetch it before the switch", s);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
-    {
-        std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
-        for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);
-        c->graphs.clear();
-        for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
-        c->cgraphs.clear();
-    }
+    RC(toggle_prologue(c, "slot %d holds a result that was not fetched: fetch it before the switch"));
     if (want && !c->b_rec_ring_host) {
         const size_t n = (size_t)lasr_ctx::TRING * c->Md;
         HIPCHK(c, hipHostMalloc((void**)&c->b_rec_ring_host, sizeof(BeamRec) * n));
@@ -2000,19 +1943,7 @@ int lasr_set_beam_records(lasr_ctx* c, int on) {
     else free_beam_recs(c);
     std::lock_guard<std::mutex> lk(c->mu);
     c->beam_rec_on = want;
-    // the host's trees and frozen prefixes keep frame / logp parallel to the tokens exactly while records are on: tokens decoded
-    // before a switch-on have no record (frame -1, log p 0); a switch-off drops them all
-    for (int s = 0; s < c->M; ++s) {
-        auto& B = c->bh[s];
-        if (want) {
-            B.frame.assign(B.par.size(), -1); B.logp.assign(B.par.size(), 0.f);
-            c->committed_recs[s].assign(c->committed[s].size(), BeamRec{-1, 0.f});
-            c->best_recs[s].assign(c->best_full[s].size(), BeamRec{-1, 0.f});
-        } else {
-            B.frame.clear(); B.logp.clear();
-            c->committed_recs[s].clear(); c->best_recs[s].clear();
-        }
-    }
+    for (auto& B : c->beams) B.set_records(want);
     return LASR_OK;
 }
 
@@ -2021,9 +1952,9 @@ int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32
     if (!c || !n_hyps) return LASR_EINVAL;
     if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_fetch_nbest serves beam search (beam > 1)");
     if (!c->beam_rec_on) return fail(c, LASR_ESTATE, "beam records are off: call lasr_set_beam_records first");
-    if (slot < 0 || slot >= c->d.max_streams || !c->open_[slot]) return fail(c, LASR_ESTATE, "slot %d is not open", slot);
+    RC(open_slot(c, slot));
     if (max_hyps < 0 || cap < 0 || (max_hyps > 0 && (!tokens || !n_tokens || !scores))) return fail(c, LASR_EINVAL, "bad argument");
-    auto& nb = c->nbest[slot];
+    const auto& nb = c->results[slot].nbest;
     const int take = std::min(max_hyps, (int)nb.size());
     bool full = false;
     for (int i = 0; i < take; ++i) full |= (int)nb[i].tokens.size() > cap;
@@ -2034,18 +1965,13 @@ int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32
         return fail(c, LASR_EFULL, "token buffers too small: need %d per hypothesis", need);
     }
     for (int i = 0; i < take; ++i) {
-        const auto& h = nb[i];
         const size_t o = (size_t)i * cap;
-        for (size_t j = 0; j < h.tokens.size(); ++j) {
-            tokens[o + j] = h.tokens[j];
-            if (frames) frames[o + j] = h.recs[j].frame;
-            if (logps) logps[o + j] = h.recs[j].logp;
-        }
-        n_tokens[i] = (int)h.tokens.size();
-        scores[i] = h.score;
+        nb[i].copy_to(tokens + o, frames ? frames + o : nullptr, logps ? logps + o : nullptr);
+        n_tokens[i] = (int)nb[i].tokens.size();
+        scores[i] = nb[i].score;
     }
     *n_hyps = (int)nb.size();
-    nb.clear(); c->queue[slot].clear(); c->rqueue[slot].clear();
+    c->results[slot].clear();
     return LASR_OK;
 }
 
@@ -2386,10 +2312,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
         }
         RC(dalloc0(c, &m.lmz[p], (size_t)M * V)); RC(dalloc0(c, &m.valid[p], M));
     }
-    for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);   // decode groups change shape
-    c->graphs.clear();
-    for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
-    c->cgraphs.clear();
+    drop_decode_graphs(c);                                              // decode groups change shape
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
     if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;
@@ -2489,10 +2412,7 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
     RC(dalloc(c, &m.gx, (size_t)M * 4 * H)); RC(dalloc(c, &m.gh, (size_t)M * 4 * H));
     RC(dalloc(c, &m.qa, (size_t)M * Kmax)); RC(dalloc(c, &m.sx, M));
     RC(dalloc(c, &m.raw, (size_t)M * V)); RC(dalloc0(c, &m.lmz[0], (size_t)M * V)); RC(dalloc0(c, &m.valid[0], M));
-    for (auto& kv : c->graphs) (void)hipGraphExecDestroy(kv.second);   // decode groups change shape
-    c->graphs.clear();
-    for (auto& kv : c->cgraphs) (void)hipGraphExecDestroy(kv.second);
-    c->cgraphs.clear();
+    drop_decode_graphs(c);                                              // decode groups change shape
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
     if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;

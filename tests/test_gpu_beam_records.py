@@ -164,6 +164,41 @@ def drive(eng, twin, slots, tslots, chunks, pipelined, on_step, depth=4, fetch=N
         collect()
 
 
+def reset_then_continue(eng, twin, slot, tslot, frozen, T0, name, W, pipelined):
+    """a predictor reset freezes the best hypothesis WITH its records; the beam restarts; the slot's frame count runs on.
+    frozen: hypothesis 0 of the slot's last model step (everything collected and fetched); T0: the frames it had consumed by then."""
+    eng.reset(slot, 1 | 2 | 4)
+    twin.reset(tslot, 1 | 2 | 4)
+    extra = synth.stream_chunks(synth.synth_pcm(3, 48000, seed=31)[1], 1280, lead=0, tail=2)[:12]
+    n_after, T, k0 = 0, T0, len(frozen[0])
+    for ch in extra:
+        if pipelined:
+            eng.push_submit([slot], ch[None])
+            twin.push_submit([tslot], ch[None])
+            ran = eng.pending()
+            assert twin.pending() == ran and ran <= 1
+            if ran:
+                assert eng.wait() == 1 and twin.wait() == 1
+        else:
+            eng.push([slot], ch[None])
+            twin.push([tslot], ch[None])
+            ran = eng.step([slot])
+            assert twin.step([tslot]) == ran
+        if not ran:
+            continue
+        T += 2
+        beam = eng.fetch_nbest(slot)
+        what = (name, W, "pipelined" if pipelined else "synchronous", "after reset", n_after)
+        same_as_fetch(beam, twin.fetch(tslot), what)          # scores[0] == -neg_logp, tokens those of the plain engine
+        check_structure(beam, T, W, 10, what)
+        for tok, fr, lp, sc in beam:
+            assert tok[:k0] == frozen[0] and list(fr[:k0]) == list(frozen[1]) and list(lp[:k0]) == list(frozen[2]), what
+            assert all(T0 <= f for f in fr[k0:]), (what, list(fr[k0:]), T0)
+        n_after += 1
+    assert max(len(h[0]) for h in beam) > k0, "no token after the reset: the frozen prefix was not continued"
+    assert n_after >= 4
+
+
 @pytest.mark.parametrize("name,W", R.SHAPES)
 def test_synchronous_streaming_whole_beam_per_model_step_then_reset(name, W):
     eng, m = engine(name, W)
@@ -183,31 +218,7 @@ def test_synchronous_streaming_whole_beam_per_model_step_then_reset(name, W):
     assert [len(h) for h in hist] == [21, 21, 21]
     if name == "tiny":
         assert len(hist[2][-1][0][0]) > 50           # the bursty stream (84 to 136 tokens per hypothesis in 3 s)
-    # a predictor reset freezes the best hypothesis WITH its records; the beam restarts; the slot's frame count runs on
-    eng.reset(slots[0], 1 | 2 | 4)
-    twin.reset(tslots[0], 1 | 2 | 4)
-    frozen = hist[0][-1][0]
-    T0 = ref[0]["T"][-1]
-    extra = synth.stream_chunks(synth.synth_pcm(3, 48000, seed=31)[1], 1280, lead=0, tail=2)[:12]
-    n_after, T, k0 = 0, T0, len(frozen[0])
-    for ch in extra:
-        eng.push([slots[0]], ch[None])
-        twin.push([tslots[0]], ch[None])
-        ran = eng.step([slots[0]])
-        assert twin.step([tslots[0]]) == ran
-        if not ran:
-            continue
-        T += 2
-        beam = eng.fetch_nbest(slots[0])
-        what = (name, W, "after reset", n_after)
-        same_as_fetch(beam, twin.fetch(tslots[0]), what)          # scores[0] == -neg_logp, tokens those of the plain engine
-        check_structure(beam, T, W, 10, what)
-        for tok, fr, lp, sc in beam:
-            assert tok[:k0] == frozen[0] and list(fr[:k0]) == list(frozen[1]) and list(lp[:k0]) == list(frozen[2]), what
-            assert all(T0 <= f for f in fr[k0:]), (what, list(fr[k0:]), T0)
-        n_after += 1
-    assert max(len(h[0]) for h in beam) > k0, "no token after the reset: the frozen prefix was not continued"
-    assert n_after >= 4
+    reset_then_continue(eng, twin, slots[0], tslots[0], hist[0][-1][0], ref[0]["T"][-1], name, W, False)
     for s in slots:
         eng.close_slot(s)
     for s in tslots:
@@ -221,15 +232,20 @@ def test_pipelined_whole_beam_per_collected_model_step(name, W):
     ref = R.stream_ref(name, W)
     slots, tslots = [eng.open() for _ in range(3)], [twin.open() for _ in range(3)]
     n_steps = [0, 0, 0]
+    last = [None, None, None]
 
     def on_step(i, beam, fetched):
         j = n_steps[i]
         same_as_fetch(beam, fetched, (name, W, "pipelined stream", i, "step", j))
         compare_step(beam, ref[i], j, W, (name, W, "pipelined stream", i, "step", j))
         n_steps[i] += 1
+        last[i] = beam
 
     drive(eng, twin, slots, tslots, R.stream_inputs(), True, on_step)
     assert n_steps == [21, 21, 21]
+    # everything is collected and fetched: the same reset tail as the synchronous test, through push_submit / wait
+    assert eng.pending() == 0 and twin.pending() == 0
+    reset_then_continue(eng, twin, slots[0], tslots[0], last[0][0], ref[0]["T"][-1], name, W, True)
     for s in slots:
         eng.close_slot(s)
     for s in tslots:
