@@ -5,24 +5,41 @@
 namespace {
 
 // the selection kernel of one beam round (+ the LM re-pick of the extended slots' tokens)
-void launch_beam_select(lasr_ctx* c, BeamState& b, int iter_slot) {
-    const int M = c->M;
+void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_slot) {
+    const int M = c->M, lp = par_rd(true, v.lm_par);        // (current-parity LM output of the hypothesis slots)
     b.lm_on = c->lm.on ? 1 : 0; b.done2 = c->c_done2;
     const float* lg = (const float*)c->logits;
     // one wave per hypothesis row (k_beam_select_rw; V <= 2048 is checked at lasr_create for beam > 1)
     // (b.rec: per-token records, lasr_set_beam_records -- an instantiation of their own, so "off" runs the kernel it always ran)
     if (b.rec) {
-        if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, true>), dim3(M), dim3(128), 0, c->stream, lg, b, iter_slot);
-        else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, true>), dim3(M), dim3(256), 0, c->stream, lg, b, iter_slot);
-        else hipLaunchKernelGGL((k_beam_select_rw<8, true>), dim3(M), dim3(512), 0, c->stream, lg, b, iter_slot);
-    } else if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, false>), dim3(M), dim3(128), 0, c->stream, lg, b, iter_slot);
-    else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, false>), dim3(M), dim3(256), 0, c->stream, lg, b, iter_slot);
-    else hipLaunchKernelGGL((k_beam_select_rw<8, false>), dim3(M), dim3(512), 0, c->stream, lg, b, iter_slot);
+        if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, true>), dim3(M), dim3(128), 0, v.stream, lg, b, iter_slot);
+        else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, true>), dim3(M), dim3(256), 0, v.stream, lg, b, iter_slot);
+        else hipLaunchKernelGGL((k_beam_select_rw<8, true>), dim3(M), dim3(512), 0, v.stream, lg, b, iter_slot);
+    } else if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, false>), dim3(M), dim3(128), 0, v.stream, lg, b, iter_slot);
+    else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, false>), dim3(M), dim3(256), 0, v.stream, lg, b, iter_slot);
+    else hipLaunchKernelGGL((k_beam_select_rw<8, false>), dim3(M), dim3(512), 0, v.stream, lg, b, iter_slot);
     if (c->lm.on)
-        LAUNCH_BEAM_FUSE(c->d.vocab, dim3(c->Md), dim3(256), 0, c->stream, (const float*)c->logits, b, iter_slot, cur_lmz(c), cur_lm_valid(c),
+        LAUNCH_BEAM_FUSE(c->d.vocab, dim3(c->Md), dim3(256), 0, v.stream, (const float*)c->logits, b, iter_slot, (const float*)c->lm.lmz[lp], (const int*)c->lm.valid[lp],
                            c->lm.alpha, c->lm.theta, c->lm.min_val);
 }
 
+// What `enqueue()` puts on stream `st`, as an instantiated graph: the one capture sequence of the library (the encoder's cell graphs,
+// the decode groups of both protocols).  Once the capture has begun it is always ended, whatever enqueue() returns; callers enqueue
+// through a view or a stream of their own, so a failure leaves every context member as it was (c: where the error text goes; null:
+// nowhere).
+template <class F>
+int capture_graph(lasr_ctx* c, hipStream_t st, F&& enqueue, hipGraphExec_t* out) {
+    hipGraph_t gr = nullptr;
+    HIPCHK(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t e = hipStreamEndCapture(st, &gr);
+    if (rc) { if (gr) (void)hipGraphDestroy(gr); return rc; }
+    if (e != hipSuccess || !gr) return fail(c, LASR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
+    e = hipGraphInstantiate(out, gr, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(gr);
+    if (e != hipSuccess) return fail(c, LASR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+    return LASR_OK;
+}
 
 // ---------------------------------------------------------------------------- command blocks
 size_t cmd_layout(lasr_ctx::Cmd& k, char* base, int M) {
@@ -63,10 +80,7 @@ int commit_T_rows(lasr_ctx* c, int T_max, bool fixed_copy = true, int* fixed_hom
     //  stream, so the cell launches of every step have the same arguments and can be replayed as a graph)
     c->T_row_dev = fixed_home ? fixed_home : c->dc.T_row;             // the command ring (NCMD blocks) outlives every step in flight
     // decode kernels of the synchronous protocols read a FIXED buffer (cached graphs replay baked-in pointers)
-    if (fixed_copy) {
-        HIPCHK(c, hipMemcpyAsync(c->T_row_fix, c->T_row_dev, sizeof(int) * c->M, hipMemcpyDeviceToDevice, c->stream));
-        c->T_row_dec = c->T_row_fix;
-    }
+    if (fixed_copy) HIPCHK(c, hipMemcpyAsync(c->T_row_fix, c->T_row_dev, sizeof(int) * c->M, hipMemcpyDeviceToDevice, c->stream));
     c->tile_masks.assign(std::max(T_max, 1), 0ull);
     for (int t = 0; t < T_max; ++t) {
         unsigned long long m = 0;
@@ -130,12 +144,11 @@ int ensure_T(lasr_ctx* c, int T) {
     dfree(c, c->x0); dfree(c, c->ybuf[0]); dfree(c, c->ybuf[1]); dfree(c, c->pe_sync);
     c->pe_sync = nullptr;
     dfree(c, c->ds.unfinished);
-    c->x0 = c->ybuf[0] = c->ybuf[1] = c->pe = nullptr; c->ds.unfinished = nullptr;
+    c->x0 = c->ybuf[0] = c->ybuf[1] = nullptr; c->ds.unfinished = nullptr;
     RC(dalloc(c, (char**)&c->x0, (size_t)cap * M * F * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[0], (size_t)cap * M * H * c->esz));
     RC(dalloc(c, (char**)&c->ybuf[1], (size_t)cap * M * H * c->esz));
     RC(dalloc0(c, &c->pe_sync, (size_t)cap * M * J));
-    c->pe = c->pe_sync;
     const int mi = std::max(c->d.max_iters_offline, c->d.max_iters_stream);
     c->tok_cap_alloc = cap * mi;
     RC(alloc_results(c));

@@ -31,7 +31,7 @@ struct lasr_ctx {
     int W = 1;                 // beam width (hypothesis slots per stream); 1 = greedy
     int Md = 0, MTd = 0;       // decoder rows = M * W (row = stream * W + slot), m-tiles
     static constexpr int LA_MAX = 4;
-    int la = 1;                // greedy lookahead: frames evaluated per row and iteration (1 with an LM or a beam)
+    // greedy lookahead: frames evaluated per row and iteration, per protocol (1 with a beam); a launch takes its value from its DecView
     int la_sync = 1;           // synchronous per-chunk protocol: 1 (groups are sized for one frame per iteration; 2 measured -4 %)
     int la_stream = 2, la_offline = 3;   // measured on configs[1] (12 steps in flight, 32-row logits tiling): streaming 2 frames per
                                // iteration f32 +2 %, bf16 +9 % (2.5 instead of 3.1 iterations per model step; 3 frames: -8 %);
@@ -85,7 +85,6 @@ struct lasr_ctx {
     int enc_par = 0;
     int pred_par = 0;               // predictor h ping-pong parity (row-major [M][H] buffers)
     void *cvt_a = nullptr, *cvt_b = nullptr;   // [M][H] element-typed staging of f32 op-level inputs
-    bool dbg_gate = true;           // decode kernels record timestamps only in the first iteration of a step
     unsigned long long* dbg = nullptr;   // LASR_DBG_TIMING: [5 kinds][4096 blocks][16] phase timestamps
     // Unused dynamic LDS given to the streaming log-mel launch (k_fe_mel: 46 592 B of its own) so that its workgroups never share a
     // CU with a workgroup of the wide decode tilings (EpiLSTMw / EpiNBRCw / EpiLinearT<4>: 66-72 KB of LDS each, launched for
@@ -112,16 +111,15 @@ struct lasr_ctx {
     int* zero_rows = nullptr;       // [M] zeros (reset passes: "no row is decoding")
     // greedy decode: predictor state after the BOS step + its joint half, captured once (see ResetArgs); LASR_BOS_CACHE=0: BOS pass per reset
     std::vector<float*> bos_h, bos_c; float* bos_pp = nullptr; bool bos_ready = false;
-    int* T_row_dec = nullptr;       // what the decode kernels read (T_row_fix; frames-available counters when continuous)
     int* T_row_fix = nullptr;       // [M] fixed-address copy of the current synchronous step's T_row: the decode kernels are
                                     // replayed from cached hipGraphs, which bake their pointer arguments in, while the
                                     // command block (T_row_dev) moves with every step
-    int* dec_t_idx = nullptr;       // frame cursor array the decode kernels use (ds.t_idx, or c_cur when continuous)
-    int pe_ring_R = 1 << 30;        // pe frame t lives at slot t % pe_ring_R
+    // Which frame cursors, frame counts, joint-half buffer and stream a decode launch uses is not context state: the synchronous
+    // protocols and the continuous loop each build a DecView (lasr_launch.hip.h: sync_view / cont_view) and hand it to the helpers.
     // continuous decode (lasr_step_submit / lasr_step_wait): front-end + encoder of later chunks run on
     // the main stream while ONE greedy loop keeps running on stream_dec across chunk boundaries: a row
     // that finished chunk k moves on to chunk k+1's frames while a bursty row is still on chunk k.
-    // a GEMM launch recorded instead of issued (launch_gemm with `cap` set): what pair launches are assembled from (k_gemm2)
+    // a GEMM launch recorded instead of issued (launch_gemm with the view's `cap` set): what pair launches are assembled from (k_gemm2)
     struct Captured {
         const void* fn = nullptr;             // the k_gemm instantiation that would have run
         unsigned gx = 0, gy = 0, threads = 0;
@@ -129,7 +127,6 @@ struct lasr_ctx {
         alignas(16) unsigned char ea[768];    // the epilogue's Args
         size_t g_size = 0, ea_size = 0;
     };
-    Captured* cap = nullptr;
     // lasr_bench_neighbour (experiment): a third stream on a hardware queue of its own, the neighbour's buffers
     hipStream_t stream_nb = nullptr; unsigned long long* nb_done = nullptr; float* nb_buf = nullptr; size_t nb_floats = 0;
     int nb_kind = 0, nb_wgs = 0; double nb_ms = 0.0;
@@ -231,7 +228,7 @@ struct lasr_ctx {
     // time-series buffers (capacity Tcap frames)
     int Tcap = 0;
     void *x0 = nullptr, *ybuf[2] = {nullptr, nullptr};   // element-typed, fragment-major
-    float *pe = nullptr, *pe_sync = nullptr;
+    float* pe_sync = nullptr;       // encoder half of the joint, synchronous protocols: [Tcap][M][J] (pipelined: pe_ring)
     int tok_cap_alloc = 0;
 
     // front-end buffers

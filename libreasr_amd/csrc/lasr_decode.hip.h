@@ -5,9 +5,9 @@
 namespace {
 
 // ---------------------------------------------------------------------------- reset
-// applies c->dc.what (already committed) to the state; runs the predictor on BOS for rows with bit 2
+// applies c->dc.what (already committed) to the state on v's stream; runs the predictor on BOS for rows with bit 2
 // plain_rows: op-level entry points address predictor rows directly (row = batch index, greedy kernels)
-int apply_reset(lasr_ctx* c, bool any_pred, int mask = 3, bool plain_rows = false) {
+int apply_reset(lasr_ctx* c, const DecView& v, bool any_pred, int mask = 3, bool plain_rows = false) {
     const bool beam = c->W > 1 && !plain_rows;
     ResetArgs a{};
     a.what = c->dc.what; a.mask = mask; a.M = c->M; a.MT = c->MT; a.H = c->d.hidden; a.Le = c->d.enc_layers; a.Lp = c->d.pred_layers;
@@ -18,8 +18,8 @@ int apply_reset(lasr_ctx* c, bool any_pred, int mask = 3, bool plain_rows = fals
         a.enc_h0[l] = c->enc[l].h0; a.enc_c0[l] = c->enc[l].c0;
     }
     for (int l = 0; l < a.Lp; ++l) {
-        a.pred_h[l] = c->pred_h[c->pred_par][l];
-        a.pred_c[l] = c->d.pred_cell ? c->pred_c[par_rd(beam, c->pred_par)][l] : nullptr;
+        a.pred_h[l] = c->pred_h[v.pred_par][l];
+        a.pred_c[l] = c->d.pred_cell ? c->pred_c[par_rd(beam, v.pred_par)][l] : nullptr;
         a.pred_h0[l] = c->pred[l].h0; a.pred_c0[l] = c->pred[l].c0;
     }
     a.token = c->ds.token; a.emit = c->ds.emit;
@@ -29,26 +29,26 @@ int apply_reset(lasr_ctx* c, bool any_pred, int mask = 3, bool plain_rows = fals
         a.bos_pp = c->bos_pp; a.pp = c->pp[0]; a.J = c->d.joint;
         any_pred = false;                    // the state after the BOS step is stored, not computed
     }
-    hipLaunchKernelGGL(k_reset_rows, dim3(grid1((size_t)c->M * c->d.hidden)), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(k_reset_rows, dim3(grid1((size_t)c->M * c->d.hidden)), dim3(256), 0, v.stream, a);
     if (c->lm.on && (mask & 2)) {      // LM state lives on the decode side, like the predictor's
         LmResetArgs la{};
         const bool lb = c->W > 1 && !plain_rows;         // beam: W slots per stream, current parity of every ping-pong buffer
         la.what = c->dc.what; la.M = c->M; la.H = c->lm.H; la.L = c->lm.L; la.bf = c->lm.q8 ? 0 : c->bf;
         la.W = lb ? c->W : 1; la.Md = lb ? c->Md : c->M;
-        const int lp = par_rd(lb, c->lm.par);
+        const int lp = par_rd(lb, v.lm_par);
         la.lm_valid = c->lm.valid[lp];
-        for (int l = 0; l < c->lm.L; ++l) { la.h[l] = c->lm.h[c->lm.par][l]; la.c[l] = c->lm.cst[lp][l]; }
+        for (int l = 0; l < c->lm.L; ++l) { la.h[l] = c->lm.h[v.lm_par][l]; la.c[l] = c->lm.cst[lp][l]; }
         if (c->lm.q8) { la.Kp = c->lm.Kp_h; for (int l = 0; l < c->lm.L; ++l) { la.qh[l] = c->lm.qh[l]; la.sxh[l] = c->lm.sxh[l]; } }
-        hipLaunchKernelGGL(k_lm_reset, dim3(grid1((size_t)c->M * c->lm.H)), dim3(256), 0, c->stream, la);
+        hipLaunchKernelGGL(k_lm_reset, dim3(grid1((size_t)c->M * c->lm.H)), dim3(256), 0, v.stream, la);
     }
     if (any_pred) {
         // T_row = 0 for every row: EpiPPJ then only refreshes pp (models.py:489: predictor(BOS))
-        int* keep_dec = c->T_row_dec;
-        c->T_row_dec = c->zero_rows;
-        HIPCHK(c, hipMemsetAsync(c->ds.t_idx, 0, sizeof(int) * c->M, c->stream));
-        launch_predictor(c, beam);
-        launch_ppj(c, beam);
-        c->T_row_dec = keep_dec;
+        DecView bos = v;
+        bos.T_row = c->zero_rows;
+        HIPCHK(c, hipMemsetAsync(c->ds.t_idx, 0, sizeof(int) * c->M, v.stream));
+        launch_predictor(c, bos, beam);
+        launch_ppj(c, bos, beam);
+        c->pred_par = bos.pred_par;
     }
     return LASR_OK;
 }
@@ -72,7 +72,9 @@ void cell_prof_harvest(lasr_ctx* c, bool all) {
 
 // ---------------------------------------------------------------------------- encoder + decode
 // Encoder over T_max frames for rows with T_row > 0 (x0 already holds LayerNorm'ed features).
-void run_encoder(lasr_ctx* c, int T_max) {
+// st: the stream it is enqueued on; pe: where the encoder half of the joint goes; pipelined: pe is the per-row frame ring of the
+// continuous loop (and the cell sequence may be replayed as a graph)
+void run_encoder(lasr_ctx* c, hipStream_t st, float* pe, bool pipelined, int T_max) {
     RoctxRange roctx_range_("lasr encoder cells");
     const int L = c->d.enc_layers;
     const int mt_total = c->Tcap * c->MT;
@@ -83,24 +85,24 @@ void run_encoder(lasr_ctx* c, int T_max) {
         cp_slot = c->cp_head;
         c->cp_head = (c->cp_head + 1) % lasr_ctx::NCELLEV;
         c->cp_cells[cp_slot] = L * T_max;
-        (void)hipEventRecord(c->cp_ev[cp_slot][0], c->stream);
+        (void)hipEventRecord(c->cp_ev[cp_slot][0], st);
     }
-    tr_mark(c, 3, c->stream);
+    tr_mark(c, 3, st);
     // layer wavefront: the cells (l, t) with l + t = d depend only on diagonal d - 1, so a diagonal is ONE launch
     // (k_gemm_multi, up to NPMAX cells): L + T - 1 launches instead of L * T, and the per-launch fixed costs of a cell
     // overlap its neighbours' K loops.  Cell (l, t) reads h parity par0 ^ (t & 1); all layers end on par0 ^ (T & 1).
     // Otherwise layer-major order: every layer starts from parity par0 and toggles T_max times (enc_h[par][l] is
     // indexed by the parity at launch time, so all layers end on par0 ^ (T_max & 1)).
-    auto enqueue_cells = [&]() {
+    auto enqueue_cells = [&](hipStream_t es) {
         if (c->enc_wave && L > 1 && T_max > 1) {
             EncCellRef cells[NPMAX];
             for (int d = 0; d < L + T_max - 1; ++d) {
                 int n = 0;
                 for (int l = std::min(d, L - 1); l >= 0 && d - l < T_max; --l) {
                     cells[n++] = EncCellRef{l, d - l};
-                    if (n == NPMAX) { launch_enc_wave(c, cells, n, par0, mt_total); n = 0; }
+                    if (n == NPMAX) { launch_enc_wave(c, es, cells, n, par0, mt_total); n = 0; }
                 }
-                if (n) launch_enc_wave(c, cells, n, par0, mt_total);
+                if (n) launch_enc_wave(c, es, cells, n, par0, mt_total);
             }
         } else {
             for (int l = 0; l < L; ++l) {
@@ -108,7 +110,7 @@ void run_encoder(lasr_ctx* c, int T_max) {
                 const void* xsrc = (l == 0) ? c->x0 : c->ybuf[(l - 1) & 1];
                 void* ydst = c->ybuf[l & 1];
                 for (int t = 0; t < T_max; ++t) {
-                    launch_enc_cell(c, l, t, xsrc, mt_total, ydst, mt_total);
+                    launch_enc_cell(c, es, l, t, xsrc, mt_total, ydst, mt_total);
                     c->enc_par ^= 1;
                 }
             }
@@ -121,7 +123,7 @@ void run_encoder(lasr_ctx* c, int T_max) {
     // stream, which cannot capture) and launched on the caller's.  Not with the in-kernel timers (a per-launch slot pointer) or
     // the debug stamps.
     bool replayed = false;
-    if (c->main_graph && c->use_graphs && c->pe == c->pe_ring && !(c->cell_prof && c->cp_slots) && !c->dbg && T_max <= 8) {
+    if (c->main_graph && c->use_graphs && pipelined && !(c->cell_prof && c->cp_slots) && !c->dbg && T_max <= 8) {
         std::vector<unsigned long long> key{(unsigned long long)T_max, (unsigned long long)par0, (unsigned long long)(uintptr_t)c->T_row_dev,
                                             (unsigned long long)(uintptr_t)c->x0, (unsigned long long)mt_total, (unsigned long long)c->enc_wave};
         for (int t = 0; t < T_max; ++t) key.push_back(c->tile_masks.empty() ? ~0ull : c->tile_masks[t]);
@@ -136,29 +138,21 @@ void run_encoder(lasr_ctx* c, int T_max) {
         }
         if (it == c->mgraphs.end()) {
             if (!c->stream_cap && hipStreamCreateWithFlags(&c->stream_cap, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-            hipGraph_t gr = nullptr;
             hipGraphExec_t ex = nullptr;
-            hipStream_t keep = c->stream;
-            if (ok && hipStreamBeginCapture(c->stream_cap, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                c->stream = c->stream_cap;
-                enqueue_cells();
-                c->stream = keep;
-                c->enc_par = par0;
-                if (hipStreamEndCapture(c->stream_cap, &gr) != hipSuccess || !gr) ok = false;
-                if (ok && hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0) != hipSuccess) ok = false;
-                if (gr) (void)hipGraphDestroy(gr);
-            } else ok = false;
+            // (no context for the error text: a failure here is answered by plain launches, not reported by the call)
+            ok = ok && capture_graph(nullptr, c->stream_cap, [&] { enqueue_cells(c->stream_cap); return LASR_OK; }, &ex) == LASR_OK;
+            c->enc_par = par0;                                                // (the capture only recorded)
             if (!ok) { (void)hipGetLastError(); c->main_graph = false; }      // (fall back to plain launches for good)
             else it = c->mgraphs.emplace(key, ex).first;
         }
-        if (ok && hipGraphLaunch(it->second, c->stream) == hipSuccess) {
+        if (ok && hipGraphLaunch(it->second, st) == hipSuccess) {
             c->enc_par = par0 ^ (T_max & 1);
             replayed = true;
         }
     }
-    if (!replayed) enqueue_cells();
-    if (cp_slot >= 0) { (void)hipEventRecord(c->cp_ev[cp_slot][1], c->stream); c->cp_n++; }
-    tr_mark(c, 4, c->stream);
+    if (!replayed) enqueue_cells(st);
+    if (cp_slot >= 0) { (void)hipEventRecord(c->cp_ev[cp_slot][1], st); c->cp_n++; }
+    tr_mark(c, 4, st);
     if (c->enclog && c->enclog_n < c->enclog_cap && 2 * T_max + 2 * L + 2 <= 32) {       // LASR_DBG_ENCLOG: checksums behind this step's cells
         RowSumArgs ra{};
         int e = 0;
@@ -168,11 +162,11 @@ void run_encoder(lasr_ctx* c, int T_max) {
         for (int t = 0; t < T_max; ++t) ra.s[e++] = RowSumSrc{c->ybuf[(L - 1) & 1], 0, mt_total, t * c->MT, c->d.hidden};
         ra.s[e++] = RowSumSrc{c->pend, 2, 0, 0, c->d.n_buffer * c->d.n_stack * c->d.n_mels};
         ra.s[e++] = RowSumSrc{c->win, 2, 0, 0, c->ring_chunks * c->d.chunk};
-        hipLaunchKernelGGL(k_dbg_rowsum, dim3(c->M, e), dim3(256), 0, c->stream, ra, c->M, c->bf,
+        hipLaunchKernelGGL(k_dbg_rowsum, dim3(c->M, e), dim3(256), 0, st, ra, c->M, c->bf,
                            c->enclog + (size_t)c->enclog_n * 32 * c->M);
         if (c->pendlog) {
             const size_t n = (size_t)c->M * c->d.n_buffer * c->d.n_stack * c->d.n_mels;
-            (void)hipMemcpyAsync(c->pendlog + (size_t)c->enclog_n * n, c->pend, sizeof(float) * n, hipMemcpyDeviceToDevice, c->stream);
+            (void)hipMemcpyAsync(c->pendlog + (size_t)c->enclog_n * n, c->pend, sizeof(float) * n, hipMemcpyDeviceToDevice, st);
         }
         c->enclog_n++;
     }
@@ -181,9 +175,75 @@ void run_encoder(lasr_ctx* c, int T_max) {
     GemmArgs g{};
     set_operand(g, 0, c->ybuf[(L - 1) & 1], mt_total, 0, 0, c->W1e);
     EpiLinear::Args ea{};
-    ea.bias = nullptr; ea.out = c->pe; ea.ldo = J; ea.n_rows = T_max * c->M; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
-    if (c->pe == c->pe_ring) { ea.ring_base = c->fe_fused ? c->c_enc_base : c->c_enc_frames; ea.ring = lasr_ctx::RING; }   // continuous mode: per-row frame ring
-    launch_linear<false, 3>(c, J / 16, T_max * c->MT, g, H, ea);
+    ea.bias = nullptr; ea.out = pe; ea.ldo = J; ea.n_rows = T_max * c->M; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
+    if (pipelined) { ea.ring_base = c->fe_fused ? c->c_enc_base : c->c_enc_frames; ea.ring = lasr_ctx::RING; }   // continuous mode: per-row frame ring
+    DecView v{};                   // (a plain linear GEMM: launch_gemm reads the stream only)
+    v.stream = st;
+    launch_linear<false, 3>(c, v, J / 16, T_max * c->MT, g, H, ea);
+}
+
+// ---------------------------------------------------------------------------- one decode iteration
+// LM branch of an iteration (LASR_LM_SIDE, pipelined protocol): forked onto stream_lm behind the selection kernel whose tokens it
+// consumes, joined in front of the next one (which reads its scores and rewrites token / emit) or at the end of the group -- the
+// predictor, the joint half and the next logits GEMM run beside it (captured: two branches of the group graph)
+struct LmSide {
+    bool open = false;
+    void join(lasr_ctx* c, const DecView& v) {
+        if (open) (void)hipStreamWaitEvent(v.stream, c->ev_lm_join, 0);
+        open = false;
+    }
+    void fork(lasr_ctx* c, DecView& v, bool beam) {
+        (void)hipEventRecord(c->ev_lm_fork, v.stream);
+        (void)hipStreamWaitEvent(c->stream_lm, c->ev_lm_fork, 0);
+        DecView lv = v;
+        lv.stream = c->stream_lm;
+        launch_lm(c, lv, beam);
+        v.lm_par = lv.lm_par;
+        (void)hipEventRecord(c->ev_lm_join, c->stream_lm);
+        open = true;
+    }
+};
+// logits -> selection -> predictor -> joint half -> LM step on v, once.  b: the beam's round (selection slot `it`), null: greedy
+// (s, slot `it`, max_iters).  side: the LM step as a branch (see LmSide) instead of in line behind the joint half.
+void decode_iteration(lasr_ctx* c, DecView& v, const DecState& s, BeamState* b, int it, int max_iters, LmSide* side = nullptr) {
+    const bool beam = b != nullptr;
+    launch_logits(c, v, c->logits, beam ? c->Md : v.la * c->M, true);
+    if (side) side->join(c, v);
+    if (beam) launch_beam_select(c, v, *b, it);
+    else launch_select<false>(v.stream, c->M, c->logits, c->d.vocab, c->d.blank, max_iters, v.T_row, s, it, nullptr, nullptr, v.la, c->M);
+    if (side) side->fork(c, v, beam);
+    launch_predictor(c, v, beam);
+    launch_ppj(c, v, beam);
+    if (!side) launch_lm(c, v, beam);
+}
+// the beam's kernel state: synchronous / offline steps (trellis and records of the step), or cont = the continuous loop (rings)
+BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
+    BeamState b{};
+    b.W = c->W; b.V = c->d.vocab; b.blank = c->d.blank; b.max_iters = max_iters; b.Md = c->Md;
+    b.t_idx = v.t_idx; b.T_row = v.T_row;
+    b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit; b.parent = c->b_parent;
+    if (!cont) {
+        b.iters = c->ds.iters; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
+        b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer
+        b.rec = c->beam_rec_on ? c->b_rec : nullptr;
+        return b;
+    }
+    b.iters = c->c_iters; b.trellis = c->b_tre_dev; b.unfinished = c->c_behind;
+    b.cont = 1; b.tring = lasr_ctx::TRING; b.frame_done = c->b_fdone_dev; b.iter_ctr = c->c_iter; b.done_blocks = c->c_done;
+    b.host_cur = c->c_hcur_dev; b.step_T = c->d.n_buffer; b.end_slots = lasr_ctx::ENDSLOTS;
+    b.end_score = c->b_endsc_dev; b.end_alive = c->b_endal_dev;
+    b.rec = c->beam_rec_on ? c->b_rec_ring_dev : nullptr;
+    return b;
+}
+// wait for a pinned flag word to leave -1: a spin instead of hipStreamSynchronize (interrupt wake-up costs ~10-20 us per round
+// trip, and there are 2-4 per step); a real sync of `st` if nothing arrives
+int spin_flag(lasr_ctx* c, volatile int* flag, hipStream_t st) {
+    unsigned long long spins = 0;
+    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == -1) {
+        __builtin_ia32_pause();
+        if (++spins > (1ull << 27)) { HIPCHK(c, hipStreamSynchronize(st)); break; }
+    }
+    return LASR_OK;
 }
 
 // Greedy decode of the current step (T_row_dev, pe ready).  Blocks until done; fills host queues.
@@ -191,8 +251,8 @@ int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const s
 
 int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::vector<int>& rows) {
     if (c->W > 1) return run_decode_beam(c, T_max, max_iters, offline, rows);
-    const int M = c->M, J = c->d.joint, V = c->d.vocab;
-    c->la = offline ? c->la_offline : c->la_sync;
+    const int M = c->M, J = c->d.joint;
+    DecView v = sync_view(c, offline ? c->la_offline : c->la_sync);
     DecState s = c->ds;
     s.tok_cap = T_max * max_iters;
     // alignment records (lasr_set_alignments): two more arrays of the step's own [M][tok_cap] shape right behind the tokens, so
@@ -212,7 +272,7 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     // (with lookahead a row consumes up to `la` blank frames per iteration: fewer iterations up front)
     constexpr int sync_first = 4;   // extra iterations of the first group
     constexpr int sync_next = 2;    // (swept in round 2: 4 + 2 best, +2 %)
-    int group = offline ? std::min(total_cap, ((T_max + c->la - 1) / c->la + 16) & ~1) : std::min(total_cap, (T_max + sync_first) & ~1);
+    int group = offline ? std::min(total_cap, ((T_max + v.la - 1) / v.la + 16) & ~1) : std::min(total_cap, (T_max + sync_first) & ~1);
     const int next_group = offline ? 32 : sync_next;
     int* res = c->res_host;
     int* ntok = res + 4;
@@ -224,23 +284,18 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
     double* logp = (double*)(((uintptr_t)(n_ones + M) + 15) & ~uintptr_t(15));
     // (the legacy NULL stream cannot be captured: graphs then only serve the pipelined path, whose
     //  decode loop runs on the ctx-owned stream_dec)
-    const bool graphs = c->use_graphs && !offline && !c->profiling && !c->dbg && c->stream != nullptr;
+    const bool graphs = c->use_graphs && !offline && !c->profiling && !c->dbg && v.stream != nullptr;
     const int buf_idx = 0;
-    auto enqueue_group = [&](int first, int n) -> int {
+    auto enqueue_group = [&](DecView& v, int first, int n) -> int {
         if (first == 0) {
-            hipLaunchKernelGGL(k_step_begin, dim3(grid1(std::max(M, c->n_iter_slots))), dim3(256), 0, c->stream, s, M,
+            hipLaunchKernelGGL(k_step_begin, dim3(grid1(std::max(M, c->n_iter_slots))), dim3(256), 0, v.stream, s, M,
                                c->n_iter_slots, offline ? 1 : 0);
-            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, c->stream, c->pe, c->pp[0], c->dec_t_idx,
-                               c->T_row_dec, c->ja, J, M, c->MTj, c->pe_ring_R, c->bf, 1, M, c->la);
+            hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)M * J)), dim3(256), 0, v.stream, v.pe, c->pp[0], v.t_idx,
+                               v.T_row, c->ja, J, M, c->MTj, v.ring, c->bf, 1, M, v.la);
         }
-        for (int q = 0; q < n; ++q) {
-            const int it = first + q;
-            c->dbg_gate = (it == 0);
-            launch_logits(c, c->logits, c->la * M, true);
-            launch_select<false>(c->stream, M, c->logits, V, c->d.blank, max_iters, c->T_row_dec, s, it, nullptr, nullptr, c->la, M);
-            launch_predictor(c);
-            launch_ppj(c);
-            launch_lm(c);
+        for (int it = first; it < first + n; ++it) {
+            v.dbg_gate = (it == 0);
+            decode_iteration(c, v, s, nullptr, it, max_iters);
         }
         // The host spins on the "rows still decoding" word in pinned memory.  Streaming: the step's tokens so far travel with it --
         // k_publish stores them into the pinned block and releases the word last (system scope).  Offline (whole utterances,
@@ -250,11 +305,11 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
         const int n_pay = M + (int)n_tokw;
         if (!offline) {
             const int nb = std::max(1, std::min(64, (n_pay + 1023) / 1024));
-            hipLaunchKernelGGL(k_publish, dim3(nb), dim3(256), 0, c->stream, (const int*)c->ds.step_ntok, c->res_dev + 4, n_pay,
+            hipLaunchKernelGGL(k_publish, dim3(nb), dim3(256), 0, v.stream, (const int*)c->ds.step_ntok, c->res_dev + 4, n_pay,
                                (const int*)(c->ds.unfinished + (first + n - 1)), c->res_dev, c->pub_arrivals);
             return LASR_OK;
         }
-        HIPCHK(c, hipMemcpyAsync(res, c->ds.unfinished + (first + n - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(res, c->ds.unfinished + (first + n - 1), sizeof(int), hipMemcpyDeviceToHost, v.stream));
         return LASR_OK;
     };
     while (iter < total_cap) {
@@ -263,37 +318,26 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
         __atomic_store_n(&res[0], -1, __ATOMIC_RELEASE);      // sentinel, overwritten by the last copy of the group (stored BEFORE anything
                                                               // of the group is enqueued: a fast group must not be overwritten by it)
         if (graphs && (n % 2) == 0) {
-            const auto key = std::make_tuple(iter, n, buf_idx, c->pred_par + 2 * c->lm.par, T_max * 1024 + max_iters);
+            const auto key = std::make_tuple(iter, n, buf_idx, v.pred_par + 2 * v.lm_par, T_max * 1024 + max_iters);
             auto it = c->graphs.find(key);
             if (it == c->graphs.end()) {
-                hipGraph_t gr = nullptr;
                 hipGraphExec_t ex = nullptr;
-                HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-                int rc = enqueue_group(iter, n);
-                hipError_t e = hipStreamEndCapture(c->stream, &gr);
-                if (rc) return rc;
-                if (e != hipSuccess || !gr) return fail(c, LASR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-                e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(gr);
-                if (e != hipSuccess) return fail(c, LASR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+                DecView rec_v = v;              // (an even group: the parities it ends on are the key's)
+                RC(capture_graph(c, v.stream, [&] { return enqueue_group(rec_v, iter, n); }, &ex));
                 it = c->graphs.emplace(key, ex).first;
             }
-            HIPCHK(c, hipGraphLaunch(it->second, c->stream));
+            HIPCHK(c, hipGraphLaunch(it->second, v.stream));
             launched = true;
         }
-        if (!launched) RC(enqueue_group(iter, n));
-        iter += n;
-        // spin on the pinned word instead of hipStreamSynchronize (interrupt wake-up costs ~10-20 us per
-        // round trip, and there are 2-4 per step); fall back to a real sync if nothing arrives.  LASR_SPIN=0: always a real sync
-        static const bool spin = !(getenv("LASR_SPIN") && atoi(getenv("LASR_SPIN")) == 0);
-        if (!spin) HIPCHK(c, hipStreamSynchronize(c->stream));
-        else {
-            unsigned long long spins = 0;
-            while (__atomic_load_n((volatile int*)&res[0], __ATOMIC_ACQUIRE) == -1) {
-                __builtin_ia32_pause();
-                if (++spins > (1ull << 27)) { HIPCHK(c, hipStreamSynchronize(c->stream)); break; }
-            }
+        if (!launched) {
+            const int rc = enqueue_group(v, iter, n);
+            c->pred_par = v.pred_par; c->lm.par = v.lm_par;      // (what was enqueued has advanced the buffers, whatever the group's tail returned)
+            RC(rc);
         }
+        iter += n;
+        static const bool spin = !(getenv("LASR_SPIN") && atoi(getenv("LASR_SPIN")) == 0);      // LASR_SPIN=0: always a real sync
+        if (!spin) HIPCHK(c, hipStreamSynchronize(v.stream));
+        else RC(spin_flag(c, &res[0], v.stream));
         if (res[0] == 0) break;
         group = next_group;
     }
@@ -330,44 +374,30 @@ int run_decode(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::v
 // are replayed on the host into the token history of every hypothesis slot.
 int run_decode_beam(lasr_ctx* c, int T_max, int max_iters, bool offline, const std::vector<int>& rows) {
     const int M = c->M, Md = c->Md, W = c->W, J = c->d.joint;
-    BeamState b{};
-    b.W = W; b.V = c->d.vocab; b.blank = c->d.blank; b.max_iters = max_iters; b.Md = Md;
-    b.t_idx = c->ds.t_idx; b.iters = c->ds.iters; b.T_row = c->T_row_dec;
-    b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit;
-    b.parent = c->b_parent; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
-    b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer
+    DecView v = sync_view(c, 1);
+    v.dbg_gate = c->dbg && getenv("LASR_DBG_BEAM");         // (LASR_DBG_TIMING + LASR_DBG_BEAM: phase stamps of the beam round's GEMMs)
+    BeamState b = beam_state(c, v, false, max_iters);
     const bool recs = c->beam_rec_on;
-    b.rec = recs ? c->b_rec : nullptr;
     const int total_cap = T_max * max_iters;
     if (total_cap + 1 > c->n_iter_slots) return fail(c, LASR_EINVAL, "decode iteration budget exceeds the trellis");
     // the records are indexed like the trellis: they must hold as many rounds as it does
     if (recs && (!c->b_rec || !c->rec_host || c->rec_slots != c->n_iter_slots))
         return fail(c, LASR_ESTATE, "beam records are on but their buffers hold %d rounds, the trellis %d", c->rec_slots, c->n_iter_slots);
     int* res = c->res_host;
-    hipLaunchKernelGGL(k_beam_begin, dim3(grid1(std::max(Md, c->n_iter_slots))), dim3(256), 0, c->stream, b, M, c->n_iter_slots);
-    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)Md * J)), dim3(256), 0, c->stream, (const float*)c->pe, (const float*)cur_pp(c),
-                       (const int*)c->dec_t_idx, (const int*)c->T_row_dec, c->ja, J, Md, c->MTj, c->pe_ring_R, c->bf, W, M, 1);
+    hipLaunchKernelGGL(k_beam_begin, dim3(grid1(std::max(Md, c->n_iter_slots))), dim3(256), 0, v.stream, b, M, c->n_iter_slots);
+    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)Md * J)), dim3(256), 0, v.stream, (const float*)v.pe, (const float*)cur_pp(c),
+                       (const int*)v.t_idx, (const int*)v.T_row, c->ja, J, Md, c->MTj, v.ring, c->bf, W, M, 1);
     int iter = 0;
     int group = offline ? std::min(total_cap, T_max + 16) : std::min(total_cap, T_max + 4);
     const int next_group = offline ? 32 : 4;
-    c->dbg_gate = c->dbg && getenv("LASR_DBG_BEAM");        // (LASR_DBG_TIMING + LASR_DBG_BEAM: phase stamps of the beam round's GEMMs)
     while (iter < total_cap) {
         const int n = std::min(group, total_cap - iter);
-        for (int q = 0; q < n; ++q) {
-            launch_logits(c, c->logits, Md, true);
-            launch_beam_select(c, b, iter + q);
-            launch_predictor(c, true);
-            launch_ppj(c, true);
-            launch_lm(c, true);
-        }
+        for (int q = 0; q < n; ++q) decode_iteration(c, v, c->ds, &b, iter + q, max_iters);
+        c->pred_par = v.pred_par; c->lm.par = v.lm_par;
         iter += n;
         __atomic_store_n(&res[0], -1, __ATOMIC_RELEASE);
-        HIPCHK(c, hipMemcpyAsync(res, c->ds.unfinished + (iter - 1), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        unsigned long long spins = 0;
-        while (__atomic_load_n((volatile int*)&res[0], __ATOMIC_ACQUIRE) == -1) {
-            __builtin_ia32_pause();
-            if (++spins > (1ull << 27)) { HIPCHK(c, hipStreamSynchronize(c->stream)); break; }
-        }
+        HIPCHK(c, hipMemcpyAsync(res, c->ds.unfinished + (iter - 1), sizeof(int), hipMemcpyDeviceToHost, v.stream));
+        RC(spin_flag(c, &res[0], v.stream));
         if (res[0] == 0) break;
         group = next_group;
     }

@@ -121,7 +121,6 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         const char* e = getenv("LASR_LOOKAHEAD");
         if (e) c->la_stream = c->la_offline = c->la_sync = std::min(lasr_ctx::LA_MAX, std::max(1, atoi(e)));
         if (c->W > 1) c->la_stream = c->la_offline = c->la_sync = 1;
-        c->la = c->la_stream;
         // beam: a model step takes ~5 selection rounds per frame; with short rounds (configs[2]: 77 us) the host round trip per
         // group is worth amortising (4 rounds per group: 13.4-13.8 -> 14.3-14.5 k audio-s/s), with long ones (configs[4]: 1024
         // hypothesis rows x 1536) the rounds launched past the need cost more (10.3 -> 10.0 k): profiles/r03/r03_experiments.txt O
@@ -384,8 +383,6 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         c->c_tok_ring = c->c_ntok_end + (size_t)M * lasr_ctx::ENDSLOTS;
     }
     c->h_frames_sub.assign(M, 0); c->h_fetched.assign(M, 0); c->h_cur_seen.assign(M, 0); c->h_avail.assign(M, 0);
-    c->dec_t_idx = c->ds.t_idx;
-    c->T_row_dec = c->T_row_dev;
     // (the reference front-end: 10 frames of 128 mels per stacked frame; other shapes take the per-chunk kernels)
     c->fe_fused = M <= 512 && d.n_buffer <= 4 && d.n_stack == 10 && d.n_mels <= 128 && d.feat == 1280 && !getenv("LASR_FE_LEGACY");
     c->h_ring_pos.assign(M, 0);
@@ -413,7 +410,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
             RC(dalloc(c, &EF, (size_t)V * H));
             GemmArgs g{}; set_operand(g, 0, emb_dev, E, 0, E / 16, wf); g.a_rows = V;
             EpiLinear::Args ea{}; ea.bias = bfn; ea.out = EF; ea.ldo = H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
-            launch_table_gemm_f32(c, H / 16, V / 16, g, ea);
+            launch_table_gemm_f32(c, sync_view(c, c->la_sync), H / 16, V / 16, g, ea);
             HIPCHK(c, hipStreamSynchronize(c->stream));
             dfree(c, wf); dfree(c, bfn);
         } else {
@@ -426,7 +423,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         RC(dalloc(c, &c->pred[0].tab, (size_t)V * G * H));
         GemmArgs g{}; set_operand(g, 0, EF, H, 0, H / 16, wt); g.a_rows = V;
         EpiLinear::Args ea{}; ea.bias = bt; ea.out = c->pred[0].tab; ea.ldo = G * H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
-        launch_table_gemm_f32(c, G * H / 16, V / 16, g, ea);
+        launch_table_gemm_f32(c, sync_view(c, c->la_sync), G * H / 16, V / 16, g, ea);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
         dfree(c, wt); dfree(c, bt); dfree(c, EF); dfree(c, emb_dev);
@@ -446,7 +443,7 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         RC(cmd_begin(c));
         c->hc.what[0] = 2;
         RC(cmd_commit(c));
-        RC(apply_reset(c, true));
+        RC(apply_reset(c, sync_view(c, c->la_sync), true));
         BosArgs b{};
         b.H = H; b.J = J; b.Lp = d.pred_layers; b.M = M; b.lstm = d.pred_cell; b.bf = c->bf;
         c->bos_h.assign(d.pred_layers, nullptr); c->bos_c.assign(d.pred_layers, nullptr);
@@ -543,20 +540,18 @@ static int reset_impl(lasr_ctx* c, const int* slots, int n, int what) {
         std::lock_guard<std::mutex> lk(c->mu);            // (decode-side launches: the pump thread stays out)
         if (c->pending.empty() && !c->group_inflight) {
             RC(order_after_decode_tail(c));          // (the last group's predictor cells may still be running on the decode stream)
-            RC(apply_reset(c, (what & 2) != 0));
+            RC(apply_reset(c, sync_view(c, c->la_sync), (what & 2) != 0));
         } else {
             // other streams have steps in flight: the encoder side of the reset is ordered on the main
             // stream, the predictor / LM side (BOS pass) on the decode stream, between two iteration groups
-            if (what & 1) RC(apply_reset(c, false, 1));
+            if (what & 1) RC(apply_reset(c, sync_view(c, c->la_sync), false, 1));
             if (what & 6) {
                 // the command block reaches the decode stream by a copy of its own: an event edge from the main stream would make
                 // the decode loop wait for everything queued there (up to `steps in flight` encoder passes, ~2 ms at depth 12)
-                hipStream_t keep = c->stream;
                 HIPCHK(c, hipMemcpyAsync((char*)c->dc.T_row, (char*)c->hc.T_row, c->cmd_bytes, hipMemcpyHostToDevice, c->stream_dec));
-                c->stream = c->stream_dec;
-                int rc = apply_reset(c, (what & 2) != 0, 2);
-                c->stream = keep;
-                if (rc) return rc;
+                DecView v = sync_view(c, c->la_sync);
+                v.stream = c->stream_dec;
+                RC(apply_reset(c, v, (what & 2) != 0, 2));
             }
         }
     }
@@ -850,9 +845,9 @@ static void frame_collected(lasr_ctx* c, int s, std::vector<int>& model_rows) {
     c->hc.T_row[s] = c->d.n_buffer;
     model_rows.push_back(s);
 }
-static void encode_step(lasr_ctx* c, int T) {
+static void encode_step(lasr_ctx* c, int T, bool pipelined = false) {
     rec(c, 1);
-    run_encoder(c, T);
+    run_encoder(c, c->stream, pipelined ? c->pe_ring : c->pe_sync, pipelined, T);
     rec(c, 2);
 }
 // tail of every synchronous step: decode the T encoded frames of `rows`, wait for the ctx stream, collect the statistics
@@ -869,7 +864,8 @@ static int decode_and_collect(lasr_ctx* c, int T, int max_iters, bool offline, c
 // LayerNorm + encoder + encoder half of the joint -- all enqueued on c->stream, nothing synchronises
 // fused (lasr_push_submit): the listed slots' newest chunk is still in the caller's buffer `fused->src` (row i of it belongs to
 // slots[i]); the front-end launch appends it to the PCM ring itself.  *fused_done tells the caller whether that happened.
-static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::vector<int>& model_rows, int& Tm,
+// pipelined: the step belongs to the continuous loop (frame ring, its own frame counters) instead of the synchronous protocol.
+static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::vector<int>& model_rows, int& Tm, bool pipelined,
                                     const PushSrc* fused = nullptr, bool* fused_done = nullptr) {
     RoctxRange roctx_range_("lasr frontend+encoder");
     const lasr_model_desc& d = c->d;
@@ -894,7 +890,7 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
         if (model_rows.empty()) return LASR_OK;
         RC(ensure_T(c, Tm));
         int* enc_frames = nullptr; int* enc_base = nullptr;
-        if (c->pe == c->pe_ring) { enc_frames = c->c_enc_frames; enc_base = c->c_enc_base; }
+        if (pipelined) { enc_frames = c->c_enc_frames; enc_base = c->c_enc_base; }
         // per (t', row): chunks pushed since the window of stacked frame t' was current; 255: the frame is already in pend
         std::vector<unsigned char> age_v((size_t)d.n_buffer * c->M, 0);
         for (int s : model_rows) {
@@ -910,7 +906,7 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
             // log-mel halves (+ the ring append of the newest chunk when fused) on 2 x n_buffer x rows workgroups, then stack + LayerNorm
             FeMelArgs m{};
             fill_fe_mel_args(c, m, c->pend);
-            int* trow_home = (c->pe == c->pe_ring) ? c->T_row_main : nullptr;      // pipelined: one fixed buffer (see commit_T_rows)
+            int* trow_home = pipelined ? c->T_row_main : nullptr;      // pipelined: one fixed buffer (see commit_T_rows)
             m.trow_out = trow_home ? trow_home : c->dc.T_row; m.enc_frames = enc_frames; m.enc_base = enc_base;
             m.src = fused ? fused->src : nullptr;
             const bool with_lazy = fused && c->lazy.on;          // (push_submit_impl: the deferred chunk belongs to exactly `slots`)
@@ -935,10 +931,10 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
             launch_fe_mel(c, m);
             if (fused_done) *fused_done = fused != nullptr;
             if (with_lazy) { c->lazy_taken++; RC(lazy_consumed(c)); }
-            RC(commit_T_rows(c, Tm, /*fixed_copy=*/c->pe != c->pe_ring, trow_home));    // the continuous loop reads its own frame counters
+            RC(commit_T_rows(c, Tm, /*fixed_copy=*/!pipelined, trow_home));    // the continuous loop reads its own frame counters
             launch_ln_tile(c, Tm);
         }
-        encode_step(c, Tm);
+        encode_step(c, Tm, pipelined);
         return LASR_OK;
     }
     bool any_feat = false;
@@ -967,9 +963,9 @@ static int enqueue_frontend_encoder(lasr_ctx* c, const int* slots, int n, std::v
     }
     if (model_rows.empty()) return LASR_OK;
     RC(ensure_T(c, Tm));
-    RC(commit_T_rows(c, Tm, /*fixed_copy=*/c->pe != c->pe_ring));    // the continuous loop reads its own frame counters
+    RC(commit_T_rows(c, Tm, /*fixed_copy=*/!pipelined));    // the continuous loop reads its own frame counters
     stack_ln_logmel(c, c->pend, d.n_buffer * d.n_stack, d.n_stack, c->T_row_dev, Tm);
-    encode_step(c, Tm);
+    encode_step(c, Tm, pipelined);
     return LASR_OK;
 }
 
@@ -983,7 +979,7 @@ int lasr_step_stream(lasr_ctx* c, const int* slots, int n, int* n_ran) {
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int> model_rows;
     int Tm = 0;
-    RC(enqueue_frontend_encoder(c, slots, n, model_rows, Tm));
+    RC(enqueue_frontend_encoder(c, slots, n, model_rows, Tm, false));
     if (model_rows.empty()) {
         HIPCHK(c, hipGetLastError());
         return LASR_OK;
@@ -1095,15 +1091,12 @@ static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fuse
         if (!c->pump_on || c->cgraphs.empty()) RC(pump_start(c));
     }
     const int idx = (int)(c->model_steps % lasr_ctx::NFLY);
-    float* pe_keep = c->pe;
-    c->pe = c->pe_ring;                     // run_encoder writes the joint's encoder half into the ring
     std::vector<int> model_rows;
     int Tm = 0;
     const bool prof = c->profiling;
     c->profiling = false;
-    int rc = enqueue_frontend_encoder(c, slots, n, model_rows, Tm, fused, fused_done);
+    int rc = enqueue_frontend_encoder(c, slots, n, model_rows, Tm, true, fused, fused_done);      // (the joint's encoder half goes into the ring)
     c->profiling = prof;
-    c->pe = pe_keep;
     if (rc) return rc;
     if (model_rows.empty()) {
         HIPCHK(c, hipGetLastError());
@@ -1235,40 +1228,23 @@ int lasr_max_inflight(const lasr_ctx* c) {
     return std::max(n, 0);
 }
 
-static int spin_flag(lasr_ctx* c, volatile int* flag, hipStream_t st) {
-    unsigned long long spins = 0;
-    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == -1) {
-        __builtin_ia32_pause();
-        if (++spins > (1ull << 27)) { HIPCHK(c, hipStreamSynchronize(st)); break; }
-    }
-    return LASR_OK;
-}
-
-// decode-side view of the ctx while the continuous loop is being fed (restored by the guard)
-struct ContScope {
-    lasr_ctx* c; hipStream_t st; float* pe; int ring; int* tidx; int* trow;
-    explicit ContScope(lasr_ctx* c_) : c(c_), st(c_->stream), pe(c_->pe), ring(c_->pe_ring_R), tidx(c_->dec_t_idx), trow(c_->T_row_dec) {
-        c->stream = c->stream_dec; c->pe = c->pe_ring; c->pe_ring_R = lasr_ctx::RING;
-        c->dec_t_idx = c->c_cur; c->T_row_dec = c->c_avail;
-    }
-    ~ContScope() { c->stream = st; c->pe = pe; c->pe_ring_R = ring; c->dec_t_idx = tidx; c->T_row_dec = trow; }
-};
-
 // ---- the decode loop of the pipelined protocol: groups of G iterations on stream_dec --------------------------------
 // Decode-side state (c->pending, h_avail, h_cur_seen, work_left, group_inflight, cont_iters, the predictor / LM parities, the
 // beam's host trees) is guarded by c->mu.  Groups are launched by the NATIVE PUMP THREAD (pump_main) while steps are in flight:
 // it spins on the pinned flag word and replays the next group's hipGraph the moment the previous one has published its cursors,
 // whatever the API thread is doing (its push_submit spends ~60 us per chunk enqueueing the front-end and the encoder cells on
 // the main stream; round 3 launched groups only from inside API calls, so a finished group waited for the host: 5 % of the
-// decode stream).  The pump never uses the launch helpers (they take the stream and the pe buffer from the ctx, which the API
-// thread is using for the main stream at that moment): its path is event waits, one admission kernel with explicit arguments
-// and a graph replay; the graphs are captured by the API thread (ensure_group_graphs) before it hands the first step over.
+// decode stream).  The pump never captures and never enqueues an iteration kernel by kernel: its path is event waits, one
+// admission kernel with explicit arguments and a graph replay.  The launch helpers would let it (everything they need comes in a
+// DecView, nothing from members another thread changes); it stays out because a capture takes milliseconds and may fail, and
+// both belong to the API call that can report it: the API thread captures every graph the pump can need (ensure_group_graphs)
+// before it hands the first step over.
 // Without graphs (LASR_NO_GRAPH, LASR_DBG_TIMING), with more than 512 slots, or with LASR_PUMP=0 there is no pump thread and
 // the API calls launch the groups themselves, as in round 3.
 
-// decode-side kernel state of the continuous loop
-static void cont_states(lasr_ctx* c, DecState& s, BeamState& bs) {
-    const int M = c->M, V = c->d.vocab;
+// decode-side kernel state of the continuous loop (v: its view)
+static void cont_states(lasr_ctx* c, const DecView& v, DecState& s, BeamState& bs) {
+    const int M = c->M;
     s = c->ds;
     s.t_idx = c->c_cur; s.iters = c->c_iters; s.step_ntok = c->c_ntotal; s.step_tok = c->c_tok_ring;
     s.tok_cap = lasr_ctx::TOKRING; s.unfinished = c->c_behind; s.cont = 1; s.host_cur = c->c_hcur_dev;
@@ -1277,103 +1253,58 @@ static void cont_states(lasr_ctx* c, DecState& s, BeamState& bs) {
     s.ntok_end = c->c_ntok_end; s.step_T = c->d.n_buffer; s.end_slots = lasr_ctx::ENDSLOTS; s.done_blocks = c->c_done;
     s.iter_ctr = c->c_iter;
     s.dbg = c->dbg ? c->dbg + ((size_t)4 * 4096 + 4095) * 16 : nullptr;
-    bs = BeamState{};
-    if (c->W > 1) {
-        bs.W = c->W; bs.V = V; bs.blank = c->d.blank; bs.max_iters = c->d.max_iters_stream; bs.Md = c->Md;
-        bs.t_idx = c->c_cur; bs.iters = c->c_iters; bs.T_row = c->c_avail;
-        bs.score = c->b_score; bs.alive = c->b_alive; bs.inB = c->b_inB; bs.token = c->ds.token; bs.emit = c->ds.emit;
-        bs.parent = c->b_parent; bs.trellis = c->b_tre_dev; bs.unfinished = c->c_behind; bs.dbg = nullptr;
-        bs.cont = 1; bs.tring = lasr_ctx::TRING; bs.frame_done = c->b_fdone_dev; bs.iter_ctr = c->c_iter; bs.done_blocks = c->c_done;
-        bs.host_cur = c->c_hcur_dev; bs.step_T = c->d.n_buffer; bs.end_slots = lasr_ctx::ENDSLOTS;
-        bs.end_score = c->b_endsc_dev; bs.end_alive = c->b_endal_dev;
-        bs.rec = c->beam_rec_on ? c->b_rec_ring_dev : nullptr;
-    }
+    bs = c->W > 1 ? beam_state(c, v, true, c->d.max_iters_stream) : BeamState{};
 }
 
-// the G iterations of a group through the launch helpers (API thread only, c->mu held, inside a ContScope): launch-invariant
-// (the flag-ring slot comes from a device counter, the last selection kernel publishes the cursors and the "rows with frames
-// left" word), so a group is one hipGraph per (G, ping-pong parities)
-static void cont_enqueue(lasr_ctx* c, int G) {
+// the G iterations of a group on v (API thread only, c->mu held): launch-invariant (the flag-ring slot comes from a device
+// counter, the last selection kernel publishes the cursors and the "rows with frames left" word), so a group is one hipGraph
+// per (G, ping-pong parities).  v ends on the parities the group leaves.
+static int cont_enqueue(lasr_ctx* c, DecView& v, int G) {
     const int M = c->M, V = c->d.vocab;
     DecState s; BeamState bs;
-    cont_states(c, s, bs);
-    c->dbg_gate = false;
-    // LM branch (stream_lm): forked behind the selection kernel whose tokens it consumes, joined in front of the next one (which
-    // reads its scores and rewrites token / emit) or at the end of the group -- the predictor, the joint half and the next
-    // logits GEMM run beside it (captured: two branches of the group graph)
-    const bool side = c->lm.on && c->stream_lm != nullptr;
+    cont_states(c, v, s, bs);
+    LmSide side_state;
+    LmSide* side = c->lm.on && c->stream_lm != nullptr ? &side_state : nullptr;
     // pair launches (LASR_LM_PAIR, greedy, fp32 / bf16 LM of >= 3 layers beside a 2 x NBRC predictor -- configs[1] with the
     // reference's LM; other shapes keep the LM step in line)
     static const int pair_env = getenv("LASR_LM_PAIR") ? atoi(getenv("LASR_LM_PAIR")) : 1;
     const bool pair = pair_env && !side && c->W == 1 && c->lm.on && !c->lm.q8 && c->d.pred_cell == 0 && c->d.pred_layers == 2 && c->lm.L >= 3;
     bool lm_tail = false;
-    bool lm_open = false;
-    auto lm_join = [&]() {
-        if (lm_open) (void)hipStreamWaitEvent(c->stream, c->ev_lm_join, 0);
-        lm_open = false;
-    };
-    auto lm_step = [&](bool beam) {
-        if (!side) { launch_lm(c, beam); return; }
-        hipStream_t keep = c->stream;
-        (void)hipEventRecord(c->ev_lm_fork, keep);
-        (void)hipStreamWaitEvent(c->stream_lm, c->ev_lm_fork, 0);
-        c->stream = c->stream_lm;
-        launch_lm(c, beam);
-        c->stream = keep;
-        (void)hipEventRecord(c->ev_lm_join, c->stream_lm);
-        lm_open = true;
-    };
     for (int q = 0; q < G; ++q) {
-        if (c->W > 1) {                 // one selection round: logits of every hypothesis slot -> ordered top-W -> predictor / joint
-            bs.host_flag = (q == G - 1) ? c->c_flag_dev : nullptr;
-            launch_logits(c, c->logits, c->Md, true);
-            lm_join();
-            launch_beam_select(c, bs, 0);
-            if (side) lm_step(true);
-            launch_predictor(c, true);
-            launch_ppj(c, true);
-            if (!side) lm_step(true);
+        (c->W > 1 ? bs.host_flag : s.host_flag) = (q == G - 1) ? c->c_flag_dev : nullptr;
+        if (!pair) {
+            decode_iteration(c, v, s, c->W > 1 ? &bs : nullptr, 0, c->d.max_iters_stream, side);
             continue;
         }
-        s.host_flag = (q == G - 1) ? c->c_flag_dev : nullptr;
-        if (pair) {
-            // LM step and predictor / joint chain of an iteration as PAIR launches (k_gemm2): LM layer l beside stage l of the chain;
-            // the step's last layers run beside the NEXT iteration's logits GEMM (or alone, at the end of the group)
-            lasr_ctx::Captured A, B;
-            auto rec = [&](lasr_ctx::Captured& k, auto&& fn) { c->cap = &k; fn(); c->cap = nullptr; };
-            if (lm_tail) {
-                rec(A, [&] { launch_logits(c, c->logits, c->la * M, true); });
-                rec(B, [&] { launch_lm(c, false, 3, 4, false); });
-                launch_pair(c, 3, false, A, B);
-                launch_lm(c, false, 4, -1);                       // deeper layers (if any), output layer, k_lm_post, parity
-                lm_tail = false;
-            } else {
-                launch_logits(c, c->logits, c->la * M, true);
-            }
-            launch_select<false>(c->stream, M, c->logits, V, c->d.blank, c->d.max_iters_stream, c->c_avail, s, 0, nullptr, nullptr, c->la, M);
-            rec(A, [&] { launch_predictor(c, false, 0, 1); });
-            rec(B, [&] { launch_lm(c, false, 0, 1, false); });
-            launch_pair(c, 0, true, A, B);
-            rec(A, [&] { launch_predictor(c, false, 1, 2); });
-            rec(B, [&] { launch_lm(c, false, 1, 2, false); });
-            launch_pair(c, 1, false, A, B);
-            rec(A, [&] { launch_ppj(c); });
-            rec(B, [&] { launch_lm(c, false, 2, 3, false); });
-            launch_pair(c, 2, false, A, B);
-            if (c->lm.L > 3) lm_tail = true;
-            else launch_lm(c, false, 3, -1);                      // (3 layers: only the output layer is left)
-            if (q == G - 1 && lm_tail) { launch_lm(c, false, 3, -1); lm_tail = false; }
-            continue;
+        // LM step and predictor / joint chain of an iteration as PAIR launches (k_gemm2): LM layer l beside stage l of the chain;
+        // the step's last layers run beside the NEXT iteration's logits GEMM (or alone, at the end of the group)
+        lasr_ctx::Captured A, B;
+        auto rec = [&](lasr_ctx::Captured& k, auto&& fn) { v.cap = &k; fn(); v.cap = nullptr; };
+        if (lm_tail) {
+            rec(A, [&] { launch_logits(c, v, c->logits, v.la * M, true); });
+            rec(B, [&] { launch_lm(c, v, false, 3, 4, false); });
+            launch_pair(c, v.stream, 3, false, A, B);
+            launch_lm(c, v, false, 4, -1);                       // deeper layers (if any), output layer, k_lm_post, parity
+            lm_tail = false;
+        } else {
+            launch_logits(c, v, c->logits, v.la * M, true);
         }
-        launch_logits(c, c->logits, c->la * M, true);
-        lm_join();
-        launch_select<false>(c->stream, M, c->logits, V, c->d.blank, c->d.max_iters_stream, c->c_avail, s, 0, nullptr, nullptr, c->la, M);
-        if (side) lm_step(false);
-        launch_predictor(c);
-        launch_ppj(c);
-        if (!side) lm_step(false);
+        launch_select<false>(v.stream, M, c->logits, V, c->d.blank, c->d.max_iters_stream, v.T_row, s, 0, nullptr, nullptr, v.la, M);
+        rec(A, [&] { launch_predictor(c, v, false, 0, 1); });
+        rec(B, [&] { launch_lm(c, v, false, 0, 1, false); });
+        launch_pair(c, v.stream, 0, true, A, B);
+        rec(A, [&] { launch_predictor(c, v, false, 1, 2); });
+        rec(B, [&] { launch_lm(c, v, false, 1, 2, false); });
+        launch_pair(c, v.stream, 1, false, A, B);
+        rec(A, [&] { launch_ppj(c, v); });
+        rec(B, [&] { launch_lm(c, v, false, 2, 3, false); });
+        launch_pair(c, v.stream, 2, false, A, B);
+        if (c->lm.L > 3) lm_tail = true;
+        else launch_lm(c, v, false, 3, -1);                      // (3 layers: only the output layer is left)
+        if (q == G - 1 && lm_tail) { launch_lm(c, v, false, 3, -1); lm_tail = false; }
     }
-    lm_join();
+    if (side) side->join(c, v);
+    return LASR_OK;
 }
 
 // the group graph for (G, current parities): captured on first use (API thread, c->mu held)
@@ -1381,20 +1312,10 @@ static int cont_group_graph(lasr_ctx* c, int G, int pred_par, int lm_par, hipGra
     const auto key = std::make_tuple(G, pred_par, lm_par);
     auto it = c->cgraphs.find(key);
     if (it == c->cgraphs.end()) {
-        const int pp0 = c->pred_par, lp0 = c->lm.par;
-        c->la = c->la_stream;
-        ContScope scope(c);
-        c->pred_par = pred_par; c->lm.par = lm_par;
-        hipGraph_t gr = nullptr;
+        DecView v = cont_view(c);                      // the capture only records: the context's parities advance at launch
+        v.pred_par = pred_par; v.lm_par = lm_par;
         hipGraphExec_t ex = nullptr;
-        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        cont_enqueue(c, G);
-        hipError_t e = hipStreamEndCapture(c->stream, &gr);
-        c->pred_par = pp0; c->lm.par = lp0;            // the capture only recorded; parities advance at launch
-        if (e != hipSuccess || !gr) return fail(c, LASR_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        e = hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(gr);
-        if (e != hipSuccess) return fail(c, LASR_EHIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+        RC(capture_graph(c, v.stream, [&] { return cont_enqueue(c, v, G); }, &ex));
         it = c->cgraphs.emplace(key, ex).first;
     }
     *out = it->second;
@@ -1470,9 +1391,9 @@ static int cont_launch_group(lasr_ctx* c, int G, bool from_pump = false) {
         { RoctxRange roctx_range_("lasr decode group"); HIPCHK(c, hipGraphLaunch(ex, sd)); }
         if (G & 1) { c->pred_par ^= 1; if (c->lm.on) c->lm.par ^= 1; }
     } else {
-        c->la = c->la_stream;
-        ContScope scope(c);
-        cont_enqueue(c, G);
+        DecView v = cont_view(c);
+        RC(cont_enqueue(c, v, G));
+        c->pred_par = v.pred_par; c->lm.par = v.lm_par;
     }
     tr_mark(c, 12, sd);
     c->tr_last_G = G;
@@ -1755,7 +1676,7 @@ int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, 
         beam_host_reset(c, s, true);
     }
     RC(cmd_commit(c));
-    RC(apply_reset(c, true));
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
     rec(c, 0);
     launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
     stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
@@ -1791,7 +1712,7 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
         beam_host_reset(c, s, true);
     }
     RC(cmd_commit(c));
-    RC(apply_reset(c, true));
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
     rec(c, 0);
     stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
     RC(commit_T_rows(c, T_max));
@@ -2009,10 +1930,10 @@ int lasr_encoder(lasr_ctx* c, const float* feats, int B, int Tp, float* out, flo
     RC(cmd_begin(c));
     for (int r = 0; r < B; ++r) { c->hc.T_row[r] = Tp; c->hc.what[r] = 1; c->hc.row_feat_off[r] = (long long)r * Tp; }
     RC(cmd_commit(c));
-    RC(apply_reset(c, false));
+    RC(apply_reset(c, sync_view(c, c->la_sync), false));
     RC(commit_T_rows(c, Tp));
     stack_ln_feats(c, feats, c->dc.row_feat_off, c->T_row_dev, Tp);
-    run_encoder(c, Tp);
+    run_encoder(c, c->stream, c->pe_sync, false, Tp);
     hipLaunchKernelGGL(k_enc_out, dim3(grid1((size_t)B * Tp * H)), dim3(256), 0, c->stream,
                        (const void*)c->ybuf[(d.enc_layers - 1) & 1], c->Tcap * c->MT, c->M, out, B, Tp, H, c->bf);
     for (int l = 0; l < d.enc_layers; ++l) {
@@ -2037,7 +1958,8 @@ int lasr_predictor(lasr_ctx* c, const int32_t* tok, int B, int U, float* out) {
     RC(cmd_begin(c));
     for (int r = 0; r < B; ++r) c->hc.what[r] = 2;
     RC(cmd_commit(c));
-    RC(apply_reset(c, false, 3, true));
+    DecView v = sync_view(c, c->la_sync);
+    RC(apply_reset(c, v, false, 3, true));
     for (int u = 0; u < U; ++u) {
         RC(cmd_begin(c));
         for (int r = 0; r < B; ++r) { c->hc.token[r] = tok[(size_t)r * U + u]; c->hc.emit[r] = 1; }
@@ -2045,8 +1967,9 @@ int lasr_predictor(lasr_ctx* c, const int32_t* tok, int B, int U, float* out) {
         if (c->Md > c->M) HIPCHK(c, hipMemsetAsync(c->ds.emit, 0, sizeof(int) * c->Md, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->ds.token, c->dc.token, sizeof(int) * c->M, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->ds.emit, c->dc.emit, sizeof(int) * c->M, hipMemcpyDeviceToDevice, c->stream));
-        launch_predictor(c);
+        launch_predictor(c, v);
     }
+    c->pred_par = v.pred_par;
     hipLaunchKernelGGL(k_from_elem, dim3(grid1((size_t)B * H)), dim3(256), 0, c->stream, (const void*)c->pred_y[0][c->d.pred_layers - 1],
                        out, (size_t)B * H, c->bf);
     HIPCHK(c, hipGetLastError());
@@ -2058,6 +1981,7 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->d.hidden, J = c->d.joint, V = c->d.vocab;
     RC(ensure_T(c, 1));
+    const DecView v = sync_view(c, c->la_sync);
     {   // pp = h_pred W1p^T + b1 ; pe[0] = h_enc W1e^T   (row-major A)
         const void* ap = h_pred; const void* ae = h_enc;
         if (c->bf) {   // bf16 operands: round the f32 inputs once
@@ -2067,13 +1991,13 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
         }
         GemmArgs g{}; set_operand(g, 0, ap, H, 0, 0, c->W1p); g.a_rows = B;
         EpiLinear::Args ea{}; ea.bias = c->b1; ea.out = c->pp[0]; ea.ldo = J; ea.n_rows = B; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = c->M;
-        launch_linear<true, 3>(c, J / 16, (B + 15) / 16, g, H, ea);
-        g.A[0] = ae; g.W[0] = c->W1e; ea.bias = nullptr; ea.out = c->pe;
-        launch_linear<true, 3>(c, J / 16, (B + 15) / 16, g, H, ea);
+        launch_linear<true, 3>(c, v, J / 16, (B + 15) / 16, g, H, ea);
+        g.A[0] = ae; g.W[0] = c->W1e; ea.bias = nullptr; ea.out = v.pe;
+        launch_linear<true, 3>(c, v, J / 16, (B + 15) / 16, g, H, ea);
     }
-    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)c->M * J)), dim3(256), 0, c->stream, (const float*)c->pe, (const float*)c->pp[0],
+    hipLaunchKernelGGL(k_ja, dim3(grid1((size_t)c->M * J)), dim3(256), 0, c->stream, (const float*)v.pe, (const float*)c->pp[0],
                        (const int*)nullptr, (const int*)nullptr, c->ja, J, c->M, c->MTj, 1 << 30, c->bf, 1, c->M, 1);
-    launch_logits(c, logits, B, false);
+    launch_logits(c, v, logits, B, false);
     if (logp_max && argmax) {
         DecState s = c->ds;
         launch_select<true>(c->stream, B, logits, V, c->d.blank, 1, nullptr, s, 0, logp_max, argmax, 1, c->M);
@@ -2293,7 +2217,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
         RC(dalloc(c, &m.cells[0].tab, (size_t)V * 4 * H));
         GemmArgs g{}; set_operand(g, 0, emb_dev, E, 0, E / 16, wt); g.a_rows = V;
         EpiLinear::Args ea{}; ea.bias = bt; ea.out = m.cells[0].tab; ea.ldo = 4 * H; ea.n_rows = V; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = M;
-        launch_table_gemm_f32(c, 4 * H / 16, V / 16, g, ea);
+        launch_table_gemm_f32(c, sync_view(c, c->la_sync), 4 * H / 16, V / 16, g, ea);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
         dfree(c, emb_dev); dfree(c, wt); dfree(c, bt);
@@ -2315,7 +2239,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
     drop_decode_graphs(c);                                              // decode groups change shape
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
-    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;
+    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la_stream = c->la_offline = c->la_sync = 1;
     c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
     m.on = true;
     RC(lm_side_setup(c));
@@ -2388,7 +2312,7 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
         RC(upload(c, &emb_dev, embed, (size_t)V * E));
         RC(dalloc(c, &qa, (size_t)V * m.Kp_ih[0])); RC(dalloc(c, &sx, V));
         RC(dalloc(c, &m.cells[0].tab, (size_t)V * 4 * H));
-        lm_q_gemv(c, emb_dev, E, E, m.Kp_ih[0], m.qWih[0], m.s_ih[0], m.b_ih[0], m.cells[0].tab, 4 * H, V, qa, sx);
+        lm_q_gemv(c, sync_view(c, c->la_sync), emb_dev, E, E, m.Kp_ih[0], m.qWih[0], m.s_ih[0], m.b_ih[0], m.cells[0].tab, 4 * H, V, qa, sx);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
         dfree(c, emb_dev); dfree(c, qa); dfree(c, sx);
@@ -2415,7 +2339,7 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
     drop_decode_graphs(c);                                              // decode groups change shape
     // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
     //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
-    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la = c->la_stream = c->la_offline = c->la_sync = 1;
+    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la_stream = c->la_offline = c->la_sync = 1;
     c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
     m.q8 = true;
     m.on = true;
@@ -2487,15 +2411,13 @@ int lasr_debug_fe_race(lasr_ctx* c, int iters, int aggressor, int per_iter, int 
     RC(dalloc(c, &log, (size_t)(iters + 1) * c->M));
     RowSumArgs ra{};
     ra.s[0] = RowSumSrc{pend_x, 2, 0, 0, d.n_buffer * d.n_stack * d.n_mels};
-    hipStream_t keep = c->stream;
+    DecView av = sync_view(c, c->la_sync);          // the aggressor's view: thrown away, the context's parities stay where they were
+    av.stream = c->stream_dec;
     auto aggress = [&]() {
-        c->stream = c->stream_dec;
-        if (aggressor == 1) launch_logits(c, c->logits, c->Md, false);
-        else if (aggressor == 2) launch_predictor(c, c->W > 1);
-        else if (aggressor == 3) launch_ppj(c, c->W > 1);
-        c->stream = keep;
+        if (aggressor == 1) launch_logits(c, av, c->logits, c->Md, false);
+        else if (aggressor == 2) launch_predictor(c, av, c->W > 1);
+        else if (aggressor == 3) launch_ppj(c, av, c->W > 1);
     };
-    const int pp0 = c->pred_par;
     for (int i = 0; i <= iters; ++i) {
         if (i > 0) for (int q = 0; q < per_iter; ++q) aggress();
         hipLaunchKernelGGL((k_fe_mel<10>), dim3(2 * d.n_buffer, c->M), dim3(320), lds_pad, c->stream, m);
@@ -2504,7 +2426,6 @@ int lasr_debug_fe_race(lasr_ctx* c, int iters, int aggressor, int per_iter, int 
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream_dec));
-    c->pred_par = pp0;
     std::vector<unsigned> h((size_t)(iters + 1) * c->M);
     hipError_t e = hipMemcpy(h.data(), log, sizeof(unsigned) * h.size(), hipMemcpyDeviceToHost);
     dfree(c, log); dfree(c, pend_x); dfree(c, trow_x);
@@ -2820,7 +2741,7 @@ int lasr_bench_cell(lasr_ctx* c, int layer, int iters, double* us) {
     RC(commit_T_rows(c, Tn));
     const void* xsrc = layer == 0 ? c->x0 : c->ybuf[(layer - 1) & 1];
     const int mt_total = c->Tcap * c->MT;
-    auto one = [&]() { launch_enc_cell(c, layer, 0, xsrc, mt_total, c->ybuf[layer & 1], mt_total); c->enc_par ^= 1; };
+    auto one = [&]() { launch_enc_cell(c, c->stream, layer, 0, xsrc, mt_total, c->ybuf[layer & 1], mt_total); c->enc_par ^= 1; };
     for (int i = 0; i < 3; ++i) one();
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));

@@ -4,9 +4,11 @@
 
 // encoder LSTM cell (layer l, step t): x from `xsrc` (fragment-major, K = I); tiling "C"
 template <class Ops>
-static void launch_enc_cell_t(lasr_ctx* c, int l, int t, const void* xsrc, int x_mt_total, void* ydst, int y_mt_total) {
+static void launch_enc_cell_t(lasr_ctx* c, hipStream_t st, int l, int t, const void* xsrc, int x_mt_total, void* ydst, int y_mt_total) {
     const Cell& L = c->enc[l];
     const int H = c->d.hidden;
+    DecView v{};                   // (launch_gemm reads the stream only)
+    v.stream = st;
     GemmArgs g{};
     set_operand(g, 0, xsrc, x_mt_total, t * c->MT, L.I / Ops::KCH, L.WxC);
     set_operand(g, 1, c->enc_h[c->enc_par][l], c->MT, 0, H / Ops::KCH, L.WhC);
@@ -28,22 +30,22 @@ static void launch_enc_cell_t(lasr_ctx* c, int l, int t, const void* xsrc, int x
     const int nw = c->cell_nw ? c->cell_nw : (Ops::BF ? 8 : 4);
     if (c->enc_u12) {
         using E12 = EpiLSTMe<Ops, 12>;
-        if (c->cell_nw == 4) launch_gemm<Ops, E12, 4, false, 3, 4>(c, H / 12, c->M / 64, g, ea);
-        else launch_gemm<Ops, E12, 4, false, 3, NW>(c, H / 12, c->M / 64, g, ea);
+        if (c->cell_nw == 4) launch_gemm<Ops, E12, 4, false, 3, 4>(c, v, H / 12, c->M / 64, g, ea);
+        else launch_gemm<Ops, E12, 4, false, 3, NW>(c, v, H / 12, c->M / 64, g, ea);
         return;
     }
-    if (nw == 4) launch_gemm<Ops, E, 2, false, 3, 4>(c, H / 8, c->M / 32, g, ea);
-    else launch_gemm<Ops, E, 2, false>(c, H / 8, c->M / 32, g, ea);
+    if (nw == 4) launch_gemm<Ops, E, 2, false, 3, 4>(c, v, H / 8, c->M / 32, g, ea);
+    else launch_gemm<Ops, E, 2, false>(c, v, H / 8, c->M / 32, g, ea);
 }
-void launch_enc_cell(lasr_ctx* c, int l, int t, const void* xsrc, int x_mt_total, void* ydst, int y_mt_total) {
-    if (c->bf) launch_enc_cell_t<OpsBF16>(c, l, t, xsrc, x_mt_total, ydst, y_mt_total);
-    else launch_enc_cell_t<OpsF32>(c, l, t, xsrc, x_mt_total, ydst, y_mt_total);
+void launch_enc_cell(lasr_ctx* c, hipStream_t st, int l, int t, const void* xsrc, int x_mt_total, void* ydst, int y_mt_total) {
+    if (c->bf) launch_enc_cell_t<OpsBF16>(c, st, l, t, xsrc, x_mt_total, ydst, y_mt_total);
+    else launch_enc_cell_t<OpsF32>(c, st, l, t, xsrc, x_mt_total, ydst, y_mt_total);
 }
 
 // One anti-diagonal of the encoder's (layer, time) grid in ONE launch: cells (l, d - l), independent of each other.
 // par0 = h ping-pong parity before the pass (cell (l, t) reads parity par0 ^ (t & 1)).
 template <class Ops>
-static void launch_enc_wave_t(lasr_ctx* c, const EncCellRef* cells, int n, int par0, int mt_total) {
+static void launch_enc_wave_t(lasr_ctx* c, hipStream_t st, const EncCellRef* cells, int n, int par0, int mt_total) {
     using E = EpiLSTM<Ops, false, false, 8>;
     const int H = c->d.hidden;
     MultiArgs<LstmArgs> m{};
@@ -69,16 +71,16 @@ static void launch_enc_wave_t(lasr_ctx* c, const EncCellRef* cells, int n, int p
     const int nw = c->cell_nw ? c->cell_nw : (Ops::BF ? 8 : 4);
     if (c->enc_u12) {
         using E12 = EpiLSTMe<Ops, 12>;
-        if (c->cell_nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, 4, false, 3>), dim3(H / 12, c->M / 64, n), dim3(256), 0, c->stream, m);
-        else hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, NW, false, 3>), dim3(H / 12, c->M / 64, n), dim3(NW * 64), 0, c->stream, m);
+        if (c->cell_nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, 4, false, 3>), dim3(H / 12, c->M / 64, n), dim3(256), 0, st, m);
+        else hipLaunchKernelGGL((k_gemm_multi<Ops, E12, 4, NW, false, 3>), dim3(H / 12, c->M / 64, n), dim3(NW * 64), 0, st, m);
         return;
     }
     const dim3 grid(H / 8, c->M / 32, n);
-    if (nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E, 2, 4, false, 3>), grid, dim3(256), 0, c->stream, m);
-    else hipLaunchKernelGGL((k_gemm_multi<Ops, E, 2, NW, false, 3>), grid, dim3(NW * 64), 0, c->stream, m);
+    if (nw == 4) hipLaunchKernelGGL((k_gemm_multi<Ops, E, 2, 4, false, 3>), grid, dim3(256), 0, st, m);
+    else hipLaunchKernelGGL((k_gemm_multi<Ops, E, 2, NW, false, 3>), grid, dim3(NW * 64), 0, st, m);
 }
-void launch_enc_wave(lasr_ctx* c, const EncCellRef* cells, int n, int par0, int mt_total) {
-    if (c->bf) launch_enc_wave_t<OpsBF16>(c, cells, n, par0, mt_total);
-    else launch_enc_wave_t<OpsF32>(c, cells, n, par0, mt_total);
+void launch_enc_wave(lasr_ctx* c, hipStream_t st, const EncCellRef* cells, int n, int par0, int mt_total) {
+    if (c->bf) launch_enc_wave_t<OpsBF16>(c, st, cells, n, par0, mt_total);
+    else launch_enc_wave_t<OpsF32>(c, st, cells, n, par0, mt_total);
 }
 

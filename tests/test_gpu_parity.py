@@ -231,6 +231,103 @@ def test_reset_semantics():
         eng.close_slot(slot)
 
 
+def _every_view_builder_vs_synchronous(case, first_slot=4):
+    """-> (per model step and stream: what fetch handed out) of a context that alternates between the protocols, and of its twin
+    that only ever took lasr_step_stream.  case: "greedy", "lm" (greedy + tiny_lm) or "beam" (width 4)."""
+    import time
+    from libreasr_amd.engine import Engine
+    cfg = synth.model_cfg("tiny")
+    sd = synth.synth_state_dict(cfg, seed=0)
+    beam = case == "beam"
+    n, CH = 4, 1280
+    pcm = synth.synth_pcm(n, 18 * CH, seed=77)
+    chunk = lambda k: np.ascontiguousarray(pcm[:, k * CH:(k + 1) * CH])
+    RESET_AT = 12                                   # chunks taken before slot 1 is reset (the end of the pipelined leg)
+    hists = []
+    for mixed in (True, False):
+        eng = Engine(sd, cfg, max_streams=16, beam=4 if beam else 1)
+        try:
+            if case == "lm":
+                eng.attach_lm(synth.synth_lm_state_dict("tiny_lm"))
+            slots = [eng.open() for _ in range(first_slot + n)][first_slot:]
+            hist = []
+
+            def fetch_step():
+                hist.append([eng.fetch(s)[0] for s in slots])
+
+            def sync(k0, k1):
+                for k in range(k0, k1):
+                    eng.push(slots, chunk(k))
+                    if eng.step(slots):
+                        fetch_step()
+
+            def collect():
+                if eng.wait():
+                    fetch_step()
+
+            if not mixed:
+                sync(0, RESET_AT)
+                eng.reset(slots[1], 7)
+                sync(RESET_AT, 18)
+                hists.append(hist)
+                continue
+            sync(0, 3)                              # (fills the streaming window: no model step yet)
+            sync(3, 6)
+            # op-level entry points: they address rows [0, B) of the decoder state directly, below the streams' rows
+            eng.predictor(np.array([[2, 5], [7, 9], [3, 1]], np.int32))
+            rng = np.random.default_rng(3)
+            eng.joint(dev(rng.standard_normal((3, cfg["hidden"])).astype(np.float32)),
+                      dev(rng.standard_normal((3, cfg["hidden"])).astype(np.float32)))
+            for k in range(6, RESET_AT):                # 6 chunks, 3 model steps in flight
+                eng.push(slots, chunk(k))
+                eng.submit(slots)
+            assert eng.pending() == 3
+            collect()
+            if not beam:
+                # decode-stream reset: slot 1's steps are decoded but uncollected, every slot still has steps in flight.
+                # (the poll only waits for the decode loop, as test_gpu_round4.py's does: nothing below depends on how long it took;
+                #  the 10 s bound turns a loop that never finishes into a failure instead of a hang)
+                t0 = time.time()
+                while True:
+                    steps, n_in = eng.peek(slots[1])
+                    if len(steps) == n_in:
+                        break
+                    assert time.time() - t0 < 10
+                assert n_in == 2 and eng.pending() == 2      # precondition of the leg (counts of uncollected steps: not timing)
+                eng.reset(slots[1], 7, if_decoded=True)
+            while eng.pending():
+                collect()
+            if beam:
+                eng.reset(slots[1], 7)
+            sync(RESET_AT, 15)
+            for k in range(15, 18):
+                eng.push(slots, chunk(k))
+                eng.submit(slots)
+            while eng.pending():
+                collect()
+            hists.append(hist)
+        finally:
+            eng.close()
+    return hists
+
+
+@pytest.mark.parametrize("case", ["greedy", "lm", "beam"])
+def test_every_view_builder_in_turn_equals_the_synchronous_protocol(case):
+    """One context through every builder of a launch view in turn -- synchronous steps, the op-level predictor and joint, six
+    chunks pipelined with three steps in flight (greedy: a decode-stream reset of slot 1 between two waits; beam: the reset
+    behind the last wait), synchronous steps again, pipelined steps again -- hands out, model step by model step and stream
+    by stream, what a twin context hands out that got the same PCM and the same reset through lasr_step_stream only: nothing a
+    launch needs may linger in the context between two builders.  Greedy: the step's tokens; beam: the best hypothesis after
+    the step (the comparison of test_gpu_beam.py between its protocols).  The streams sit on slots 4..7: the op-level entry
+    points address rows [0, B) of the decoder state directly, as they always have."""
+    got, want = _every_view_builder_vs_synchronous(case)
+    assert len(got) == len(want) == 8
+    for j, (a, b) in enumerate(zip(got, want)):
+        for s in range(4):
+            assert a[s] == b[s], (case, j, s, a[s], b[s])
+    assert sum(len(t) for step in want for t in step) > 0
+
+
 def test_error_codes():
     from libreasr_amd._native import LasrError
     eng, _, _ = engine("tiny")

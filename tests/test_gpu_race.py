@@ -92,22 +92,38 @@ def test_encoder_side_of_a_pipelined_run_equals_the_synchronous_run(name, W, B, 
 
 
 def test_log_mel_kernel_beside_each_decode_kernel():
-    eng, cfg = _engine("cfg5", 8, 128, "bf16")
-    try:
-        B = 128
-        assert eng.config("fe_lds_pad") > 0            # the wide decode tilings can run in this context
-        slots = [eng.open() for _ in range(B)]
-        pcm = np.stack([synth.synth_pcm(1, 8 * 1280, seed=1234 + s)[0] for s in range(B)])
-        for k in range(8):
+    B = 128
+    pcm = np.stack([synth.synth_pcm(1, 10 * 1280, seed=1234 + s)[0] for s in range(B)])
+
+    def feed(eng, slots, k0, k1):                      # synchronous steps over chunks [k0, k1) -> what the last one handed out
+        last = None
+        for k in range(k0, k1):
             eng.push(slots, pcm[:, k * 1280:(k + 1) * 1280])
             if eng.step(slots):
-                eng.fetch_many(slots, 8192)
+                last = eng.fetch_many(slots, 8192)
+        return last
+
+    eng, cfg = _engine("cfg5", 8, 128, "bf16")
+    try:
+        assert eng.config("fe_lds_pad") > 0            # the wide decode tilings can run in this context
+        slots = [eng.open() for _ in range(B)]
+        feed(eng, slots, 0, 8)
         for agg, nm in ((0, "nothing"), (1, "vocabulary GEMM"), (2, "predictor pass"), (3, "joint half")):
             bl, br = eng.debug_fe_race(300, agg, 4)
             print(f"beside {nm}: {bl} of 300 launches differ ({br} rows)")
             assert (bl, br) == (0, 0)
+        # the probe's decode launches go through a view that is thrown away: the ping-pong parities are where they were, and the
+        # next synchronous step hands out what it does in a context that was never probed
+        after = feed(eng, slots, 8, 10)
     finally:
         eng.close()
+    eng, cfg = _engine("cfg5", 8, 128, "bf16")
+    try:
+        slots = [eng.open() for _ in range(B)]
+        want = feed(eng, slots, 0, 10)
+    finally:
+        eng.close()
+    assert after is not None and after == want
 
 
 def test_wide_tilings_do_not_disturb_even_without_the_lds_pad():
