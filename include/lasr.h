@@ -272,6 +272,39 @@ int lasr_set_beam_records(lasr_ctx* c, int on);
 int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32_t* frames, float* logps, int cap,
                      int* n_tokens, double* scores, int* n_hyps);
 
+/* ---- Forced alignment and transcript scoring: the teacher-forced RNN-T lattice.  Replaces Transducer.forward (models.py:308-359:
+ * log_softmax(joint(pred[u], enc[t])) for every (t, u)) followed by the forward algorithm of the loss (loss.py:77-79), for inference:
+ * only the two entries per cell that the recursion reads are produced, and no gradient.
+ * One utterance has T encoder frames f_0..f_{T-1} and labels y_1..y_U (U >= 0, every id in [0, vocab) and not blank).  g_0 = the
+ * predictor on BOS from the learned initial state, g_u = the predictor stepped on y_u: what the offline greedy path feeds the joint
+ * after it has emitted y_1..y_u.  lp[t,u,:] = log_softmax(joint(g_u, f_t)); b[t,u] = lp[t,u,blank] (0 <= u <= U);
+ * e[t,u] = lp[t,u,y_{u+1}] (0 <= u < U).
+ *   alpha[0,0] = 0; alpha[t,u] = logaddexp(alpha[t-1,u] + b[t-1,u], alpha[t,u-1] + e[t,u-1]) (a missing predecessor counts -inf)
+ *   loglik  = alpha[T-1,U] + b[T-1,U] = log P(y | x) summed over all alignments = -rnnt_loss of loss.py
+ *   viterbi = the same recursion with max, final blank included; the emission predecessor (t, u-1) wins only if it is STRICTLY
+ *             greater than the blank predecessor (t-1, u): a tie takes the blank
+ *   frames[u-1] = the frame t_u on which the best path takes e[t_u, u-1] (non-decreasing); logps[u-1] = e[t_u, u-1]
+ * The lattice is the standard unconstrained one: the greedy loop's per-frame cap (max_iters) is NOT applied.  A capped greedy run can
+ * therefore report a -neg_logp ABOVE the best lattice path of its own tokens (numpy oracle, tiny_lstm, 3.0 s: -20.39 against -37.68):
+ * at a capped frame the greedy loop moves on without paying a blank.  Operand type, rounding points and accumulation of the joint are
+ * the context's (dtype); b and e are f32 -- the log-softmax in the decode path's own order of operations, so given the same logits a
+ * term IS the log p that lasr_fetch_aligned reports for the same predictor state and frame (the logits GEMM may run on another tiling
+ * than the decode loop's: last bits); alpha, loglik and viterbi are accumulated in double on the device.
+ * An attached LM plays no part: the lattice is the joint's.
+ * Audio arguments as for lasr_transcribe_pcm / lasr_transcribe_feats (host or device, the same length checks).  tokens: the n transcripts
+ * concatenated, HOST memory, n_tokens[i] = U_i <= 1535.  All outputs are HOST memory, filled before the call returns: loglik [n] (required);
+ * viterbi [n], frames [sum U_i], logps [sum U_i] (each optional; the Viterbi pass is skipped when all three are null); blank_lp / emit_lp
+ * (optional): per utterance [T_i][U_i + 1] f32 each, concatenated; column U_i of emit_lp is 0.
+ * Like lasr_transcribe_*, the call needs an idle context (LASR_ESTATE otherwise), starts every listed slot from fresh state, clears the
+ * slot's uncollected results, and leaves the slots as lasr_stream_reset(.., 1 | 2 | 4) would: a lasr_transcribe_* or streaming run on the
+ * same slot afterwards gives the result it gives without the call.  LASR_EINVAL, nothing changed: a token out of range or equal to blank,
+ * n_tokens[i] < 0 or too large, n > max_streams, beam > 1 (a beam context lays its predictor rows out per hypothesis slot; left for a
+ * follow-up).  Workspaces are allocated at the first call and grow on demand; everything runs on the ctx stream. */
+int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                   const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp);
+int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                     const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */
@@ -289,6 +322,12 @@ int lasr_predictor(lasr_ctx* c, const int32_t* tok, int B, int U, float* out);
  * logp_max [B], argmax [B] (device). */
 int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, float* logits,
                float* logp_max, int32_t* argmax);
+
+/* The lattice dynamic programme alone (see lasr_align_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
+ * [T_i][U_i + 1] f32, concatenated (column U_i of emit_lp is not read); T, U: HOST int32 [n] (T >= 1, 0 <= U <= 1535).  Results in HOST
+ * memory, filled before the call returns (this one synchronises): loglik [n] (required), viterbi [n], frames [sum U_i] (optional). */
+int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
+                    double* loglik, double* viterbi, int32_t* frames);
 
 /* ---- timing / introspection ------------------------------------------------------------------ */
 typedef struct {

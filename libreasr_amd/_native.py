@@ -71,6 +71,9 @@ SYMBOLS = [
     ("lasr_fetch_many_aligned", C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     ("lasr_set_beam_records", C.c_int, [_P, C.c_int]),
     ("lasr_fetch_nbest", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_int)]),
+    ("lasr_align_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("lasr_align_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("lasr_lattice_dp", C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
     ("lasr_logmel", C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     ("lasr_stack", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     ("lasr_encoder", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

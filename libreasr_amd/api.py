@@ -104,6 +104,51 @@ class LibreASR:
             out = ids if return_ids else [self.lang.denumericalize(i) for i in ids]
         return out if isinstance(audio, (list, tuple)) else out[0]
 
+    def _ids(self, transcript):
+        """A transcript as token ids: a sequence of ids, or text when the language object can numericalize."""
+        if isinstance(transcript, str):
+            if not hasattr(self.lang, "numericalize"):
+                raise TypeError("this language object cannot numericalize text: pass token ids")
+            transcript = self.lang.numericalize(transcript)
+        return [int(t) for t in transcript]
+
+    def align(self, audio, transcript):
+        """Forced alignment of a transcript the caller already has (the teacher-forced RNN-T lattice; greedy engines).  transcript: a
+        list of non-blank token ids, or text when the language object can numericalize; lists of utterances / transcripts are batched.
+        -> {"score": log P(transcript | audio) summed over all alignments, "viterbi": the best alignment's log-probability,
+        "tokens": [(token_id, time_s, confidence)]} with time_s the start of the 80 ms encoder frame the token falls on in the best
+        alignment and confidence the joint's probability of the token there."""
+        many = isinstance(audio, (list, tuple))
+        batch = list(audio) if many else [audio]
+        ys = [self._ids(t) for t in (transcript if many else [transcript])]
+        if len(ys) != len(batch):
+            raise ValueError("one transcript per utterance")
+        slots = [self.engine.open() for _ in batch]
+        try:
+            res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys)
+        finally:
+            for s in slots:
+                self.engine.close_slot(s)
+        out = [{"score": r["loglik"], "viterbi": r["viterbi"], "tokens": self._aligned(y, r["frames"], r["logps"])} for r, y in zip(res, ys)]
+        return out if many else out[0]
+
+    def score(self, audio, candidates):
+        """log P(candidate | audio), summed over all alignments, of every candidate transcript of ONE utterance (rescoring an n-best
+        list): one engine call per group of up to max_streams candidates.  The audio is encoded again for every candidate; a
+        shared encoder pass belongs with the lattice on beam engines."""
+        ys = [self._ids(t) for t in candidates]
+        pcm = self._utterance(audio)
+        out, g = [], self.engine.max_streams
+        for i in range(0, len(ys), g):
+            part = ys[i:i + g]
+            slots = [self.engine.open() for _ in part]
+            try:
+                out += [r["loglik"] for r in self.engine.align_pcm(slots, [pcm] * len(part), part, viterbi=False)]
+            finally:
+                for s in slots:
+                    self.engine.close_slot(s)
+        return out
+
     def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the
         hypothesis so far after every model call.

@@ -331,6 +331,23 @@ struct lasr_ctx {
     hipEvent_t tr_base = nullptr;
     std::atomic<int> tr_n{0};
 
+    // teacher-forced lattice (lasr_align_* / lasr_lattice_dp, lasr_lattice.hip.h): workspaces, all null until the first such call;
+    // they grow through ensure_buf
+    struct Lattice {
+        float* pp = nullptr; size_t pp_n = 0;             // lat_pp [U_max + 1][rows][J]: the joint's predictor half per label position
+        char* ja = nullptr; size_t ja_n = 0;              // block activations, fragment-major, element-typed: LAT_R rows
+        float* logits = nullptr; size_t logits_n = 0;     // block logits [LAT_R][V]
+        float* b = nullptr; size_t b_n = 0;               // [cells] blank terms
+        float* e = nullptr; size_t e_n = 0;               // [cells] label terms
+        long long* tab = nullptr; size_t tab_n = 0;       // per-call tables (LatTab + back-pointer offsets)
+        double* res = nullptr; size_t res_n = 0;          // [2 n] loglik, viterbi
+        int* frames = nullptr; size_t frames_n = 0;       // [sum U]
+        float* logps = nullptr; size_t logps_n = 0;
+        unsigned* bp = nullptr; size_t bp_n = 0;          // back-pointer words of the utterances that do not fit in LDS
+        hipEvent_t ev[5] = {}; bool ev_ok = false;
+        int us[4] = {0, 0, 0, 0};     // lasr_set_profiling: front-end + encoder, predictor, lattice blocks, DP of the last call (us)
+    } lat;
+
     // stats
     bool profiling = false;
     hipEvent_t ev[8];

@@ -18,6 +18,7 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_cmd.hip.h"
 #include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
+#include "lasr_lattice.hip.h"
 #include "lasr_weights.hip.h"
 
 
@@ -91,6 +92,8 @@ void lasr_destroy(lasr_ctx* c) {
     for (auto& e : c->ev_enc)
         if (e) (void)hipEventDestroy(e);
     if (c->ev_misc) (void)hipEventDestroy(c->ev_misc);
+    if (c->lat.ev_ok)
+        for (auto& e : c->lat.ev) (void)hipEventDestroy(e);
     if (c->cp_ok)
         for (auto& p : c->cp_ev)
             for (auto& e : p) (void)hipEventDestroy(e);
@@ -1720,6 +1723,115 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
     return decode_and_collect(c, T_max, d.max_iters_offline, true, std::vector<int>(slots, slots + n));
 }
 
+// ---------------------------------------------------------------------------- teacher-forced lattice
+// common head of lasr_align_*: a greedy, idle context, open slots, a valid transcript per utterance -- nothing has changed when it fails
+static int align_prologue(lasr_ctx* c, const int* slots, int n, const void* audio, const void* lens, const int32_t* tokens,
+                          const int32_t* n_tokens, const double* loglik) {
+    if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_align_*: greedy contexts only (beam = %d)", c->W);
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    RC(check_slots(c, slots, n, true));
+    if (n == 0) return LASR_OK;
+    if (!audio || !lens || !loglik) return fail(c, LASR_EINVAL, "null argument");
+    return lat_check_tokens(c, n, tokens, n_tokens);
+}
+int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                   const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+    if (!c) return LASR_EINVAL;
+    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, loglik));
+    if (n == 0) return LASR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const lasr_model_desc& d = c->d;
+    long long total = 0; int T_max = 0; int Tmel_max = 0;
+    std::vector<int> Tp(n), Tm(n);
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] <= d.n_fft / 2) return fail(c, LASR_EINVAL, "utterance %d too short (%lld samples)", i, (long long)n_samples[i]);
+        Tm[i] = 1 + (int)(n_samples[i] / d.hop);
+        if (Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
+        Tp[i] = (Tm[i] - d.n_stack) / d.stride + 1;
+        T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
+        total += n_samples[i];
+    }
+    RC(ensure_T(c, T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
+    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        c->hc.T_row[s] = Tp[i]; c->hc.what[s] = 7; c->hc.row_frames[s] = Tm[i];
+        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
+        off += n_samples[i];
+        c->results[s].clear(); c->results[s].neg_logp = 0.0;
+    }
+    RC(cmd_commit(c));
+    lat_mark(c, c->lat, 0);
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
+    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
+    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return lat_finish(c, slots, n, Tp.data(), tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp});
+}
+int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                     const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+    if (!c) return LASR_EINVAL;
+    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, loglik));
+    if (n == 0) return LASR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const lasr_model_desc& d = c->d;
+    long long total = 0; int T_max = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
+        T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
+    }
+    RC(ensure_T(c, T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        c->hc.T_row[s] = n_frames[i]; c->hc.what[s] = 7; c->hc.row_feat_off[s] = off;
+        off += n_frames[i];
+        c->results[s].clear(); c->results[s].neg_logp = 0.0;
+    }
+    RC(cmd_commit(c));
+    lat_mark(c, c->lat, 0);
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
+    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return lat_finish(c, slots, n, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp});
+}
+// the dynamic programme alone, on the caller's lattices (host or device); T, U and the results are host memory; blocking
+int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
+                    double* viterbi, int32_t* frames) {
+    if (!c) return LASR_EINVAL;
+    if (!blank_lp || !emit_lp || !T || !U || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
+    LatCall k;
+    k.n = n;
+    k.T.assign(T, T + n); k.U.assign(U, U + n); k.slot.assign(n, 0);
+    for (int i = 0; i < n; ++i)
+        if (T[i] < 1 || U[i] < 0 || U[i] > LAT_UMAX) return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d (T >= 1, 0 <= U <= %d)", i, T[i], U[i], LAT_UMAX);
+    HIPCHK(c, hipSetDevice(c->device));
+    lasr_ctx::Lattice& w = c->lat;
+    std::vector<long long> img;
+    RC(lat_upload(c, w, k, nullptr, img));
+    const float *b = nullptr, *e = nullptr;
+    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
+    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
+    const bool vit = viterbi || frames;
+    RC(lat_run_dp(c, w, k, b, e, vit, frames != nullptr, false));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
+    return LASR_OK;
+}
+
 // Transducer.transcribe_stream on feature chunks (models.py:506-575): carried encoder / predictor
 // state, max_iters_stream.  feats [n, T, feat] (host or device), the same T for every listed slot.
 int lasr_step_feats(lasr_ctx* c, const int* slots, int n, const float* feats, int T) {
@@ -2718,6 +2830,8 @@ int lasr_debug_config(lasr_ctx* c, const char* key, int* value) {
         {"cell_nw", c->cell_nw ? c->cell_nw : (c->bf ? 8 : 4)}, {"use_graphs", (int)c->use_graphs}, {"M", c->M},
         {"push_lazy", (int)c->lazy_on}, {"pump_nap_pct", c->pump_nap_pct}, {"lazy_taken", c->lazy_taken}, {"lazy_flushed", c->lazy_flushed},
         {"fe_lds_pad", c->fe_lds_pad}, {"roctx", roctx_state().push != nullptr ? 1 : 0},
+        {"lat_R", LAT_R}, {"lat_umax", LAT_UMAX},      // lattice (lasr_align_*): rows per block, labels per transcript; with profiling on,
+        {"lat_enc_us", c->lat.us[0]}, {"lat_pred_us", c->lat.us[1]}, {"lat_blocks_us", c->lat.us[2]}, {"lat_dp_us", c->lat.us[3]},   // the last call's stages
     };
     for (const auto& e : tab)
         if (!strcmp(e.k, key)) { *value = e.v; return LASR_OK; }

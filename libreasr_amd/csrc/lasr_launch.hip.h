@@ -94,7 +94,7 @@ template <class Ops> void launch_predictor_t(lasr_ctx* c, DecView& v, bool beam,
 template <class Ops> void launch_ppj_t(lasr_ctx* c, DecView& v, bool beam);
 template <class Ops> void launch_lm_t(lasr_ctx* c, DecView& v, bool beam, int l0, int l1, bool tail);
 template <class Ops> bool launch_pair_ops(hipStream_t st, int kind, bool lm_first, lasr_ctx::Captured& A, lasr_ctx::Captured& B);
-template <class Ops> void launch_logits_ops(lasr_ctx* c, const DecView& v, float* out, int n_rows, bool gated);
+template <class Ops> void launch_logits_ops(lasr_ctx* c, const DecView& v, const void* act, int mtj, int row_cap, float* out, int n_rows, bool gated);
 template <class Ops, bool AROW, int D> void launch_linear_ops(lasr_ctx* c, const DecView& v, int n_groups, int m_groups, GemmArgs g, int K, const EpiLinear::Args& ea);
 void launch_lm_q8(lasr_ctx* c, DecView& v);                                // (integer-valued bf16 operands whatever the model's type: bf16 unit)
 // quantise `rows` rows of src -> integer GEMV -> dequantise (+ bias) into out; also builds the int8-served LM's token table at attach
@@ -106,7 +106,7 @@ void launch_table_gemm_f32(lasr_ctx* c, const DecView& v, int n_groups, int m_gr
     X template void launch_ppj_t<Ops>(lasr_ctx*, DecView&, bool);                                                           \
     X template void launch_lm_t<Ops>(lasr_ctx*, DecView&, bool, int, int, bool);                                            \
     X template bool launch_pair_ops<Ops>(hipStream_t, int, bool, lasr_ctx::Captured&, lasr_ctx::Captured&);                 \
-    X template void launch_logits_ops<Ops>(lasr_ctx*, const DecView&, float*, int, bool);                                   \
+    X template void launch_logits_ops<Ops>(lasr_ctx*, const DecView&, const void*, int, int, float*, int, bool);                \
     X template void launch_linear_ops<Ops, true, -1>(lasr_ctx*, const DecView&, int, int, GemmArgs, int, const EpiLinear::Args&);  \
     X template void launch_linear_ops<Ops, false, -1>(lasr_ctx*, const DecView&, int, int, GemmArgs, int, const EpiLinear::Args&); \
     X template void launch_linear_ops<Ops, true, 3>(lasr_ctx*, const DecView&, int, int, GemmArgs, int, const EpiLinear::Args&);   \
@@ -145,8 +145,13 @@ inline void launch_linear(lasr_ctx* c, const DecView& v, int n_groups, int m_gro
     else launch_linear_ops<OpsF32, AROW, D>(c, v, n_groups, m_groups, g, K, ea);
 }
 inline void launch_logits(lasr_ctx* c, const DecView& v, float* out, int n_rows, bool gated) {
-    if (c->bf) launch_logits_ops<OpsBF16>(c, v, out, n_rows, gated);
-    else launch_logits_ops<OpsF32>(c, v, out, n_rows, gated);
+    if (c->bf) launch_logits_ops<OpsBF16>(c, v, c->ja, c->MTj, c->Md, out, n_rows, gated);
+    else launch_logits_ops<OpsF32>(c, v, c->ja, c->MTj, c->Md, out, n_rows, gated);
+}
+// the same GEMM over an activation buffer of the caller's (mtj m-tiles, row_cap rows), every row < n_rows (the lattice blocks)
+inline void launch_logits_from(lasr_ctx* c, const DecView& v, const void* act, int mtj, int row_cap, float* out, int n_rows) {
+    if (c->bf) launch_logits_ops<OpsBF16>(c, v, act, mtj, row_cap, out, n_rows, false);
+    else launch_logits_ops<OpsF32>(c, v, act, mtj, row_cap, out, n_rows, false);
 }
 
 // k_lm_post / k_beam_fuse with the register slots their vocabulary needs (bit-identical either way, see k_lm_post)

@@ -63,11 +63,12 @@ static void launch_logits_t(lasr_ctx* c, const DecView& v, const GemmArgs& g0, i
     const int ng = c->d.vocab / 16, mg = (n_rows + 16 * MTL - 1) / (16 * MTL);
     launch_gemm<Ops, EpiLinear, MTL, false, -1>(c, v, ng, mg, g, ea);
 }
+// act: the fragment-major activations (mtj m-tiles, row_cap rows): c->ja / c->MTj / c->Md for the decode loops, a block buffer for the lattice
 template <class Ops>
-void launch_logits_ops(lasr_ctx* c, const DecView& v, float* out, int n_rows, bool gated) {
+void launch_logits_ops(lasr_ctx* c, const DecView& v, const void* act, int mtj, int row_cap, float* out, int n_rows, bool gated) {
     const int J = c->d.joint, V = c->d.vocab;
     GemmArgs g{};
-    set_operand(g, 0, c->ja, c->MTj, 0, 0, c->W2); g.M = c->Md;
+    set_operand(g, 0, act, mtj, 0, 0, c->W2); g.M = row_cap;
     g.dbg = (c->dbg && v.dbg_gate) ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;
     EpiLinear::Args ea{};
     ea.bias = c->b2; ea.out = out; ea.ldo = V; ea.n_rows = n_rows;

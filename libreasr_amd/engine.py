@@ -375,6 +375,100 @@ class Engine:
         nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
         self._chk(self.lib.lasr_transcribe_feats(self.ctx, p, n, _ptr(cat), nf.ctypes.data_as(C.c_void_p)))
 
+    # ------------------------------------------------------------------ forced alignment / transcript scoring
+    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi):
+        a, p, n = self._slots(slots)
+        assert len(token_lists) == n
+        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+        U = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        loglik = np.zeros(n, dtype=np.float64)
+        vit = np.zeros(n, dtype=np.float64) if viterbi else None
+        fr = np.zeros(max(int(tok.size), 1), dtype=np.int32) if viterbi else None
+        lp = np.zeros(max(int(tok.size), 1), dtype=np.float32) if viterbi else None
+        b = e = None
+        if lattice:      # T_i is what the library derives from the audio: the encoder frames of the utterance
+            Ts = self._align_frames(lens, fn is self.lib.lasr_align_pcm)
+            cells = int(sum(int(t) * (int(u) + 1) for t, u in zip(Ts, U)))
+            b, e = np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32)
+        self._chk(fn(self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p),
+                     U.ctypes.data_as(C.c_void_p), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e)))
+        out, o, oc = [], 0, 0
+        for i in range(n):
+            u = int(U[i])
+            r = {"loglik": float(loglik[i])}
+            if viterbi:
+                r.update(viterbi=float(vit[i]), frames=fr[o:o + u].copy(), logps=lp[o:o + u].copy())
+            if lattice:
+                t = int(Ts[i])
+                r.update(blank_lp=b[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(), emit_lp=e[oc:oc + t * (u + 1)].reshape(t, u + 1).copy())
+                oc += t * (u + 1)
+            o += u
+            out.append(r)
+        return out
+
+    def _align_frames(self, lens, pcm):
+        d = self.desc
+        if not pcm:
+            return [int(v) for v in lens]
+        return [((1 + int(v) // d.hop) - d.n_stack) // d.stride + 1 for v in lens]
+
+    def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True):
+        """Teacher-forced RNN-T lattice of every (utterance, transcript) pair (lasr_align_pcm): pcm_list as for transcribe_pcm,
+        token_lists[i] = non-blank ids.  -> per utterance {"loglik": log P(y | x) over all alignments, "viterbi": best path's score,
+        "frames" / "logps": per label the encoder frame it falls on and the joint's log p there}; lattice=True adds "blank_lp" /
+        "emit_lp" [T, U + 1] float32; viterbi=False skips the alignment pass (scoring only).  The slots are left freshly reset."""
+        a, p, n = self._slots(slots)
+        assert len(pcm_list) == n
+        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
+            cat = torch.cat([x.reshape(-1).float() for x in pcm_list]).contiguous()
+        else:
+            cat = np.ascontiguousarray(np.concatenate([
+                np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
+                for x in pcm_list]))
+        ns = np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
+        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi)
+
+    def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True):
+        """align_pcm from stacked features (lasr_align_feats): feats_list as for transcribe_feats."""
+        a, p, n = self._slots(slots)
+        assert len(feats_list) == n
+        F = self.desc.feat
+        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
+            cat = torch.cat([x.reshape(-1, F).float() for x in feats_list]).contiguous()
+            nf = [x.reshape(-1, F).shape[0] for x in feats_list]
+        else:
+            arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
+            cat = np.ascontiguousarray(np.concatenate(arrs))
+            nf = [a_.shape[0] for a_ in arrs]
+        nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
+        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi)
+
+    def lattice_dp(self, blank, emit, viterbi=True):
+        """The lattice dynamic programme alone (lasr_lattice_dp) on caller-supplied lattices: blank / emit = lists of [T_i, U_i + 1]
+        float32 arrays (column U_i of emit is not read).  -> per lattice {"loglik", "viterbi", "frames"}."""
+        n = len(blank)
+        assert n == len(emit) and n >= 1
+        bs = [np.asarray(x, dtype=np.float32) for x in blank]
+        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
+        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
+        U = np.ascontiguousarray(np.array([x.shape[1] - 1 for x in bs], dtype=np.int32))
+        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
+        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        loglik = np.zeros(n, dtype=np.float64)
+        vit = np.zeros(n, dtype=np.float64) if viterbi else None
+        fr = np.zeros(max(int(U.sum()), 1), dtype=np.int32) if viterbi else None
+        self._chk(self.lib.lasr_lattice_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(U), n, _ptr(loglik), _ptr(vit), _ptr(fr)))
+        out, o = [], 0
+        for i in range(n):
+            r = {"loglik": float(loglik[i])}
+            if viterbi:
+                r.update(viterbi=float(vit[i]), frames=fr[o:o + int(U[i])].copy())
+            o += int(U[i])
+            out.append(r)
+        return out
+
     # ------------------------------------------------------------------ op-level (tests, microbench)
     def logmel(self, pcm):
         """pcm [B, N] cuda float32 -> [B, T, n_mels]"""

@@ -1,0 +1,52 @@
+"""What does a forced alignment cost?  (run on the GPU box)
+cfg2 (synthetic weights), the 20.65 s demo utterance with the engine's own greedy transcript, lasr_align_pcm at n = 1 and n = 8:
+HIP events around the call, median of 20 runs after 3 warm-up runs, and the per-stage times the engine records with profiling on
+(front-end + encoder, teacher-forced predictor, lattice blocks, dynamic programme).  The lattice blocks are dominated by the logits
+GEMM: cells x 2 J V flop, set against the f32 MFMA peak (157.3 TFLOP/s, MI355X data sheet).
+    python tools/lattice_cost.py [f32|bf16]"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from libreasr_amd import flac, synth
+from libreasr_amd.engine import Engine
+
+PEAK_F32_MFMA = 157.3e12
+dtype = sys.argv[1] if len(sys.argv) > 1 else "f32"
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pcm, sr, _ = flac.decode(os.path.join(root, "tests", "golden", "demo_3729-6852-0035.flac"))
+assert sr == 16000
+cfg = synth.model_cfg("cfg2")
+eng = Engine(synth.synth_state_dict(cfg), cfg, max_streams=8, dtype=dtype)
+slots = [eng.open() for _ in range(8)]
+dev_pcm = torch.as_tensor(np.ascontiguousarray(pcm, np.float32)).to(eng.device)
+eng.transcribe_pcm(slots[:1], [dev_pcm])
+y = eng.fetch(slots[0])[0]
+out = {"dtype": dtype, "seconds": round(len(pcm) / sr, 2), "labels": len(y), "lat_R": eng.config("lat_R")}
+eng.set_profiling(True)
+for n in (1, 8):
+    ms, stages = [], []
+    for rep in range(23):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = eng.align_pcm(slots[:n], [dev_pcm] * n, [y] * n)
+        e1.record()
+        e1.synchronize()
+        if rep >= 3:
+            ms.append(e0.elapsed_time(e1))
+            stages.append([eng.config(k) for k in ("lat_enc_us", "lat_pred_us", "lat_blocks_us", "lat_dp_us")])
+    T = (1 + len(pcm) // 160 - 10) // 8 + 1
+    cells = n * T * (len(y) + 1)
+    st = np.median(np.asarray(stages, np.float64), axis=0)
+    flop = cells * 2.0 * cfg["joint"] * cfg["vocab"]
+    out[f"n{n}"] = {"T": T, "cells": cells, "call_ms_median": round(float(np.median(ms)), 3),
+                    "encoder_ms": round(st[0] / 1e3, 3), "predictor_ms": round(st[1] / 1e3, 3), "blocks_ms": round(st[2] / 1e3, 3),
+                    "dp_ms": round(st[3] / 1e3, 3), "gemm_gflop": round(flop / 1e9, 1),
+                    "blocks_fraction_of_f32_mfma_peak": round(flop / (st[2] * 1e-6) / PEAK_F32_MFMA, 4) if st[2] else None,
+                    "loglik": res[0]["loglik"], "viterbi": res[0]["viterbi"]}
+eng.close()
+print(json.dumps(out))
