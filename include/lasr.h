@@ -305,6 +305,40 @@ int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const
 int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
                      const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp);
 
+/* ---- N-best rescoring: one encoder pass per utterance and the lattice over a prefix tree of its candidates.
+ * lasr_prefix_tree (host only: no context, no GPU) merges k >= 1 candidates -- tokens: concatenated, n_tokens[j] labels each -- into
+ * a tree.  Node 0 is the empty prefix (parent -1, label -1, depth 0); every distinct non-empty prefix is one node; label[v] is the
+ * label that leads from parent[v] to v, depth[v] the length of the prefix.  Order: depth ascending; within a depth parent ascending;
+ * within a parent by first appearance (lowest candidate index).  Hence parent[v] < v, depth is non-decreasing, the nodes of one depth
+ * are contiguous and so are the children of a node.  term[j] (k entries) is the node of candidate j: duplicates share a node, an empty
+ * candidate maps to node 0.  parent / label / depth hold cap entries.  *n_nodes is always set (0 on LASR_EINVAL).  LASR_EFULL: cap is
+ * too small, nothing else is written; LASR_EINVAL: a null argument, a negative length, k < 1. */
+int lasr_prefix_tree(const int32_t* tokens, const int32_t* n_tokens, int k, int cap, int32_t* parent, int32_t* label, int32_t* depth,
+                     int32_t* term, int* n_nodes);
+
+/* lasr_score_*: log P(candidate | audio) of every candidate of n utterances (terms, recursions and number formats as lasr_align_*).
+ * Utterance i has n_cands[i] >= 1 candidates; slots, n_tokens, loglik and viterbi are [sum n_cands], grouped by utterance; tokens: all
+ * candidates concatenated in that order (HOST).  Every candidate occupies one open, distinct slot -- its predictor row -- so
+ * sum n_cands <= max_streams; the audio of utterance i (pcm / n_samples or feats / n_frames: n entries, as for lasr_align_*) is
+ * encoded once, on the slot of its first candidate.  The candidates of an utterance are merged by lasr_prefix_tree (N_i nodes) and each
+ * distinct (frame, prefix) goes through the joint once; one dynamic programme over the tree gives every node v
+ *   alpha[0,0] = 0; alpha[t,v] = logaddexp(alpha[t-1,v] + b[t-1,v], alpha[t,parent v] + e[t,v]);  final[v] = alpha[T-1,v] + b[T-1,v]
+ * = log P(prefix_v | x), with b[t,v] = lp[t,v,blank] and e[t,v] = lp[t,parent v,label v] -- the emission that ENTERS v, e[t,0] = 0 --
+ * and viterbi the same with max (a tie takes the blank).  loglik[j] / viterbi[j] = final[term[j]]: duplicate candidates get equal
+ * results.  For a single candidate the rows, blocks and operations are lasr_align_*'s: blank_lp is bit-equal, emit_lp's column u + 1
+ * is align's column u, loglik and viterbi are equal.
+ * Outputs, HOST memory, filled before the call returns: loglik (required); viterbi (optional: the Viterbi half is skipped when null);
+ * blank_lp / emit_lp (optional): per utterance [T_i][N_i] f32, concatenated, N_i as lasr_prefix_tree reports it.  No frames and no
+ * back-pointers: lasr_align_* aligns a chosen candidate.
+ * Idle context (LASR_ESTATE otherwise); every listed slot starts from fresh state, loses its uncollected results and is left as
+ * lasr_stream_reset(.., 1 | 2 | 4) would leave it, as with lasr_align_*.  LASR_EINVAL, nothing changed: a token out of range or equal
+ * to blank, n_tokens[j] < 0 or > 1535, n_cands[i] < 1, a slot listed twice, sum n_cands > max_streams, N_i > 2048, beam > 1 (a beam
+ * context's predictor rows are hypothesis slots with their own reset and parity rules; left for a follow-up). */
+int lasr_score_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* n_cands,
+                   const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp);
+int lasr_score_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* n_cands,
+                     const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */
@@ -328,6 +362,14 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
  * memory, filled before the call returns (this one synchronises): loglik [n] (required), viterbi [n], frames [sum U_i] (optional). */
 int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
                     double* loglik, double* viterbi, int32_t* frames);
+
+/* The tree dynamic programme alone (see lasr_score_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
+ * [T_i][N_i] f32, concatenated (emit_lp[t][0] is not read); T, n_nodes [n] and parent [sum N_i] (ids local to the lattice): HOST int32.
+ * LASR_EINVAL unless T >= 1, 1 <= N <= 2048, parent[0] == -1, 0 <= parent[v] < v and the depth derived from parent is non-decreasing.
+ * Results per NODE in HOST memory, [sum N_i], filled before the call returns (this one synchronises): loglik (required), viterbi
+ * (optional). */
+int lasr_lattice_tree_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* n_nodes,
+                         const int32_t* parent, int n, double* loglik, double* viterbi);
 
 /* ---- timing / introspection ------------------------------------------------------------------ */
 typedef struct {

@@ -134,8 +134,8 @@ class LibreASR:
 
     def score(self, audio, candidates):
         """log P(candidate | audio), summed over all alignments, of every candidate transcript of ONE utterance (rescoring an n-best
-        list): one engine call per group of up to max_streams candidates.  The audio is encoded again for every candidate; a
-        shared encoder pass belongs with the lattice on beam engines."""
+        list): one engine call per group of up to max_streams candidates.  The audio is encoded again for every candidate:
+        `rescore` encodes it once per group and shares the candidates' common prefixes."""
         ys = [self._ids(t) for t in candidates]
         pcm = self._utterance(audio)
         out, g = [], self.engine.max_streams
@@ -148,6 +148,27 @@ class LibreASR:
                 for s in slots:
                     self.engine.close_slot(s)
         return out
+
+    def rescore(self, audio, candidates, viterbi=False):
+        """log P(candidate | audio), summed over all alignments, of every candidate transcript of ONE utterance, in the candidates'
+        order (text or ids, as in `score`), over a prefix tree of the candidates: per group of up to max_streams candidates one
+        engine call that encodes the audio once and sends every distinct (frame, prefix) through the joint once (greedy engines).
+        viterbi=True: -> (scores, best-alignment log-probabilities)."""
+        ys = [self._ids(t) for t in candidates]
+        pcm = self._utterance(audio)
+        out, vit, g = [], [], self.engine.max_streams
+        for i in range(0, len(ys), g):
+            part = ys[i:i + g]
+            slots = [self.engine.open() for _ in part]
+            try:
+                r = self.engine.score_pcm([slots], [pcm], [part], viterbi=viterbi)[0]
+            finally:
+                for s in slots:
+                    self.engine.close_slot(s)
+            out += [float(v) for v in r["loglik"]]
+            if viterbi:
+                vit += [float(v) for v in r["viterbi"]]
+        return (out, vit) if viterbi else out
 
     def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the

@@ -331,8 +331,9 @@ struct lasr_ctx {
     hipEvent_t tr_base = nullptr;
     std::atomic<int> tr_n{0};
 
-    // teacher-forced lattice (lasr_align_* / lasr_lattice_dp, lasr_lattice.hip.h): workspaces, all null until the first such call;
-    // they grow through ensure_buf
+    // teacher-forced lattice (lasr_align_* / lasr_lattice_dp, lasr_lattice.hip.h; over a prefix tree: lasr_score_* /
+    // lasr_lattice_tree_dp, lasr_lattice_tree.hip.h, where u reads "node"): workspaces, all null until the first such call; they grow
+    // through ensure_buf
     struct Lattice {
         float* pp = nullptr; size_t pp_n = 0;             // lat_pp [U_max + 1][rows][J]: the joint's predictor half per label position
         char* ja = nullptr; size_t ja_n = 0;              // block activations, fragment-major, element-typed: LAT_R rows
@@ -340,7 +341,7 @@ struct lasr_ctx {
         float* b = nullptr; size_t b_n = 0;               // [cells] blank terms
         float* e = nullptr; size_t e_n = 0;               // [cells] label terms
         long long* tab = nullptr; size_t tab_n = 0;       // per-call tables (LatTab + back-pointer offsets)
-        double* res = nullptr; size_t res_n = 0;          // [2 n] loglik, viterbi
+        double* res = nullptr; size_t res_n = 0;          // [2 n] loglik, viterbi (tree: [2 nodes], per node)
         int* frames = nullptr; size_t frames_n = 0;       // [sum U]
         float* logps = nullptr; size_t logps_n = 0;
         unsigned* bp = nullptr; size_t bp_n = 0;          // back-pointer words of the utterances that do not fit in LDS

@@ -19,6 +19,8 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
 #include "lasr_lattice.hip.h"
+#include "lasr_prefix_tree.hip.h"
+#include "lasr_lattice_tree.hip.h"
 #include "lasr_weights.hip.h"
 
 
@@ -1829,6 +1831,161 @@ int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, co
     HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
+    return LASR_OK;
+}
+
+// ---------------------------------------------------------------------------- n-best rescoring over a prefix tree
+int lasr_prefix_tree(const int32_t* tokens, const int32_t* n_tokens, int k, int cap, int32_t* parent, int32_t* label, int32_t* depth,
+                     int32_t* term, int* n_nodes) {
+    return lasr_pt::prefix_tree(tokens, n_tokens, k, cap, parent, label, depth, term, n_nodes);
+}
+// common head of lasr_score_*: a greedy, idle context, one open slot and a valid transcript per candidate, a tree per utterance that
+// fits -- nothing has changed when it fails.  *K = candidates of the call
+static int score_prologue(lasr_ctx* c, const int* slots, int n, const void* audio, const void* lens, const int32_t* n_cands,
+                          const int32_t* tokens, const int32_t* n_tokens, const double* loglik, int* K, std::vector<lasr_pt::Tree>& trees) {
+    *K = 0;
+    if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_score_*: greedy contexts only (beam = %d)", c->W);
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    if (n < 0 || n > c->d.max_streams) return fail(c, LASR_EINVAL, "bad utterance count (n=%d)", n);
+    if (n == 0) return LASR_OK;
+    if (!n_cands) return fail(c, LASR_EINVAL, "null argument");
+    int k = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_cands[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has %d candidates (>= 1)", i, n_cands[i]);
+        if (n_cands[i] > c->d.max_streams - k) return fail(c, LASR_EINVAL, "more candidates than max_streams (%d)", c->d.max_streams);
+        k += n_cands[i];
+    }
+    RC(check_slots(c, slots, k, true));
+    if (!audio || !lens || !loglik) return fail(c, LASR_EINVAL, "null argument");
+    RC(lat_check_tokens(c, k, tokens, n_tokens));
+    trees.resize(n);
+    long long at = 0;
+    for (int i = 0, j = 0; i < n; j += n_cands[i], ++i) {
+        lasr_pt::build(tokens + at, n_tokens + j, n_cands[i], trees[i]);
+        if ((int)trees[i].parent.size() > LAT_NMAX)
+            return fail(c, LASR_EINVAL, "utterance %d: the candidates' prefix tree has %d nodes (<= %d)", i, (int)trees[i].parent.size(), LAT_NMAX);
+        for (int q = 0; q < n_cands[i]; ++q) at += n_tokens[j + q];
+    }
+    *K = k;
+    return LASR_OK;
+}
+int lasr_score_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* n_cands,
+                   const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp) {
+    if (!c) return LASR_EINVAL;
+    int K = 0;
+    std::vector<lasr_pt::Tree> trees;
+    RC(score_prologue(c, slots, n, pcm, n_samples, n_cands, tokens, n_tokens, loglik, &K, trees));
+    if (n == 0) return LASR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const lasr_model_desc& d = c->d;
+    long long total = 0; int T_max = 0; int Tmel_max = 0;
+    std::vector<int> Tp(n), Tm(n);
+    for (int i = 0; i < n; ++i) {
+        if (n_samples[i] <= d.n_fft / 2) return fail(c, LASR_EINVAL, "utterance %d too short (%lld samples)", i, (long long)n_samples[i]);
+        Tm[i] = 1 + (int)(n_samples[i] / d.hop);
+        if (Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
+        Tp[i] = (Tm[i] - d.n_stack) / d.stride + 1;
+        T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
+        total += n_samples[i];
+    }
+    RC(ensure_T(c, T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
+    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0, j = 0; i < n; ++i) {
+        const int s = slots[j];                       // the audio lives on the row of the first candidate; the others keep T_row = 0
+        c->hc.T_row[s] = Tp[i]; c->hc.row_frames[s] = Tm[i];
+        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
+        off += n_samples[i];
+        for (int q = 0; q < n_cands[i]; ++q, ++j) {
+            c->hc.what[slots[j]] = 7;
+            c->results[slots[j]].clear(); c->results[slots[j]].neg_logp = 0.0;
+        }
+    }
+    RC(cmd_commit(c));
+    lat_mark(c, c->lat, 0);
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
+    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
+    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return tree_finish(c, slots, n, n_cands, Tp.data(), tokens, n_tokens, trees, TreeOut{loglik, viterbi, blank_lp, emit_lp});
+}
+int lasr_score_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* n_cands,
+                     const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp) {
+    if (!c) return LASR_EINVAL;
+    int K = 0;
+    std::vector<lasr_pt::Tree> trees;
+    RC(score_prologue(c, slots, n, feats, n_frames, n_cands, tokens, n_tokens, loglik, &K, trees));
+    if (n == 0) return LASR_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const lasr_model_desc& d = c->d;
+    long long total = 0; int T_max = 0;
+    for (int i = 0; i < n; ++i) {
+        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
+        T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
+    }
+    RC(ensure_T(c, T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0, j = 0; i < n; ++i) {
+        c->hc.T_row[slots[j]] = n_frames[i]; c->hc.row_feat_off[slots[j]] = off;      // (the first candidate's row; the others: T_row = 0)
+        off += n_frames[i];
+        for (int q = 0; q < n_cands[i]; ++q, ++j) {
+            c->hc.what[slots[j]] = 7;
+            c->results[slots[j]].clear(); c->results[slots[j]].neg_logp = 0.0;
+        }
+    }
+    RC(cmd_commit(c));
+    lat_mark(c, c->lat, 0);
+    RC(apply_reset(c, sync_view(c, c->la_offline), true));
+    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
+    RC(commit_T_rows(c, T_max));
+    encode_step(c, T_max);
+    return tree_finish(c, slots, n, n_cands, n_frames, tokens, n_tokens, trees, TreeOut{loglik, viterbi, blank_lp, emit_lp});
+}
+// the tree dynamic programme alone, on the caller's lattices (host or device); T, n_nodes, parent and the results are host memory; blocking
+// (contiguous children are NOT required here: only k_lat_dp_tree runs, which reads parent / depth / dstart; the child tables that
+// tree_upload derives are valid for lasr_prefix_tree's order alone and are not to be used behind this entry point)
+int lasr_lattice_tree_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* n_nodes,
+                         const int32_t* parent, int n, double* loglik, double* viterbi) {
+    if (!c) return LASR_EINVAL;
+    if (!blank_lp || !emit_lp || !T || !n_nodes || !parent || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
+    TreeCall k;
+    k.n = n;
+    k.T.assign(T, T + n); k.N.assign(n_nodes, n_nodes + n);
+    long long no = 0;
+    for (int i = 0; i < n; ++i) {
+        if (T[i] < 1 || n_nodes[i] < 1 || n_nodes[i] > LAT_NMAX)
+            return fail(c, LASR_EINVAL, "lattice %d: T = %d, N = %d (T >= 1, 1 <= N <= %d)", i, T[i], n_nodes[i], LAT_NMAX);
+        const int32_t* p = parent + no;
+        if (p[0] != -1) return fail(c, LASR_EINVAL, "lattice %d: node 0 is the root (parent -1)", i);
+        k.parent.push_back(-1); k.depth.push_back(0);
+        for (int v = 1; v < n_nodes[i]; ++v) {
+            if (p[v] < 0 || p[v] >= v) return fail(c, LASR_EINVAL, "lattice %d: parent[%d] = %d (0 <= parent < node)", i, v, p[v]);
+            const int dv = k.depth[(size_t)no + p[v]] + 1;
+            if (dv < k.depth.back()) return fail(c, LASR_EINVAL, "lattice %d: node %d is shallower than node %d (depth must not decrease)", i, v, v - 1);
+            k.parent.push_back(p[v]); k.depth.push_back(dv);
+        }
+        no += n_nodes[i];
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    lasr_ctx::Lattice& w = c->lat;
+    std::vector<long long> img;
+    RC(tree_upload(c, w, k, img));
+    const float *b = nullptr, *e = nullptr;
+    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
+    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
+    RC(tree_run_dp(c, w, k, b, e, viterbi != nullptr));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
+    if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + k.nodes, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
     return LASR_OK;
 }
 

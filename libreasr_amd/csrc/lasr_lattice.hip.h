@@ -261,11 +261,48 @@ int lat_check_tokens(lasr_ctx* c, int n, const int32_t* tokens, const int32_t* n
     return LASR_OK;
 }
 
+// Teacher-forced predictor of the listed rows into w.pp [Umax + 1][Ml][J]: g_0 is the BOS pass of apply_reset; g_u = the predictor
+// stepped on y_u (rows whose transcript has ended: emit = 0, their state is carried and their column of lat_pp is never read).
+// tokens: the n transcripts concatenated, U[i] labels each
+int lat_teacher_force(lasr_ctx* c, lasr_ctx::Lattice& w, DecView& v, const int* slots, int n, const std::vector<int>& U, int Umax,
+                      const int32_t* tokens, int Ml) {
+    const int M = c->M, J = c->d.joint, H = c->d.hidden, L = c->d.pred_layers;
+    HIPCHK(c, hipMemcpyAsync(w.pp, c->pp[0], sizeof(float) * (size_t)Ml * J, hipMemcpyDeviceToDevice, c->stream));
+    long long at0 = 0;
+    std::vector<long long> first(n);
+    for (int i = 0; i < n; ++i) { first[i] = at0; at0 += U[i]; }
+    for (int u = 1; u <= Umax; ++u) {
+        RC(cmd_begin(c));
+        for (int i = 0; i < n; ++i)
+            if (u <= U[i]) { c->hc.token[slots[i]] = tokens[first[i] + u - 1]; c->hc.emit[slots[i]] = 1; }
+        RC(cmd_commit(c));
+        HIPCHK(c, hipMemcpyAsync(c->ds.token, c->dc.token, sizeof(int) * M, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ds.emit, c->dc.emit, sizeof(int) * M, hipMemcpyDeviceToDevice, c->stream));
+        launch_predictor(c, v);
+        c->pred_par = v.pred_par;
+        GemmArgs g{};
+        set_operand(g, 0, c->pred_y[0][L - 1], H, 0, 0, c->W1p); g.a_rows = Ml;
+        EpiLinear::Args ea{};
+        ea.bias = c->b1; ea.out = w.pp + (size_t)u * Ml * J; ea.ldo = J; ea.n_rows = Ml; ea.M = M;
+        launch_linear<true, 3>(c, v, J / 16, (Ml + 15) / 16, g, H, ea);
+    }
+    return LASR_OK;
+}
+// stage times of the call from the events lat_mark recorded (stream idle)
+void lat_times(lasr_ctx* c, lasr_ctx::Lattice& w) {
+    if (!c->profiling || !w.ev_ok) return;
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, w.ev[i], w.ev[i + 1]) != hipSuccess) (void)hipGetLastError();
+        w.us[i] = (int)(1e3f * ms + 0.5f);
+    }
+}
+
 // Behind the front-end and the encoder of a lasr_align_* call (pe_sync holds the joint's encoder half, the listed slots are in the
 // state apply_reset left them in: predictor stepped on BOS, its joint half in pp[0]): teacher-forced predictor, lattice blocks,
 // dynamic programme, results to the host, slots back to fresh state.
 int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int32_t* tokens, const int32_t* n_tokens, const LatOut& o) {
-    const int M = c->M, J = c->d.joint, V = c->d.vocab, H = c->d.hidden, L = c->d.pred_layers;
+    const int M = c->M, J = c->d.joint, V = c->d.vocab;
     lasr_ctx::Lattice& w = c->lat;
     LatCall k;
     k.n = n;
@@ -280,28 +317,9 @@ int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int
     RC(ensure_buf(c, &w.logits, &w.logits_n, (size_t)LAT_R * V));
     RC(ensure_buf(c, &w.b, &w.b_n, (size_t)k.cells));
     RC(ensure_buf(c, &w.e, &w.e_n, (size_t)k.cells));
-    // ---- teacher-forced predictor: g_0 is the BOS pass of apply_reset; g_u = the predictor stepped on y_u (rows whose transcript
-    // has ended: emit = 0, their state is carried and their column of lat_pp is never read)
+    // ---- teacher-forced predictor
     DecView v = sync_view(c, 1);
-    HIPCHK(c, hipMemcpyAsync(w.pp, c->pp[0], sizeof(float) * (size_t)Ml * J, hipMemcpyDeviceToDevice, c->stream));
-    long long at0 = 0;
-    std::vector<long long> first(n);
-    for (int i = 0; i < n; ++i) { first[i] = at0; at0 += k.U[i]; }
-    for (int u = 1; u <= k.Umax; ++u) {
-        RC(cmd_begin(c));
-        for (int i = 0; i < n; ++i)
-            if (u <= k.U[i]) { c->hc.token[slots[i]] = tokens[first[i] + u - 1]; c->hc.emit[slots[i]] = 1; }
-        RC(cmd_commit(c));
-        HIPCHK(c, hipMemcpyAsync(c->ds.token, c->dc.token, sizeof(int) * M, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->ds.emit, c->dc.emit, sizeof(int) * M, hipMemcpyDeviceToDevice, c->stream));
-        launch_predictor(c, v);
-        c->pred_par = v.pred_par;
-        GemmArgs g{};
-        set_operand(g, 0, c->pred_y[0][L - 1], H, 0, 0, c->W1p); g.a_rows = Ml;
-        EpiLinear::Args ea{};
-        ea.bias = c->b1; ea.out = w.pp + (size_t)u * Ml * J; ea.ldo = J; ea.n_rows = Ml; ea.M = M;
-        launch_linear<true, 3>(c, v, J / 16, (Ml + 15) / 16, g, H, ea);
-    }
+    RC(lat_teacher_force(c, w, v, slots, n, k.U, k.Umax, tokens, Ml));
     lat_mark(c, w, 2);
     // ---- lattice blocks
     for (long long cell0 = 0; cell0 < k.cells; cell0 += LAT_R) {
@@ -330,12 +348,7 @@ int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int
     if (o.logps && k.sumU) HIPCHK(c, hipMemcpy(o.logps, w.logps, sizeof(float) * (size_t)k.sumU, hipMemcpyDeviceToHost));
     if (o.blank_lp) HIPCHK(c, hipMemcpy(o.blank_lp, w.b, sizeof(float) * (size_t)k.cells, hipMemcpyDeviceToHost));
     if (o.emit_lp) HIPCHK(c, hipMemcpy(o.emit_lp, w.e, sizeof(float) * (size_t)k.cells, hipMemcpyDeviceToHost));
-    if (c->profiling && w.ev_ok)
-        for (int i = 0; i < 4; ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, w.ev[i], w.ev[i + 1]) != hipSuccess) (void)hipGetLastError();
-            w.us[i] = (int)(1e3f * ms + 0.5f);
-        }
+    lat_times(c, w);
     return LASR_OK;
 }
 

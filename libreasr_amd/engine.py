@@ -469,6 +469,120 @@ class Engine:
             out.append(r)
         return out
 
+    # ------------------------------------------------------------------ n-best rescoring over a prefix tree
+    def prefix_tree(self, token_lists):
+        """The candidates merged into a prefix tree (lasr_prefix_tree; host only).  -> {"parent", "label", "depth": int32 [N],
+        "term": int32 [k], the node of every candidate}: node 0 is the empty prefix, parent[v] < v, depth non-decreasing, the
+        children of a node contiguous."""
+        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+        k = len(toks)
+        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        cap = int(nt.sum()) + 1
+        par, lab, dep = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        term = np.zeros(max(k, 1), dtype=np.int32)
+        n = C.c_int(0)
+        rc = self.lib.lasr_prefix_tree(_ptr(tok), _ptr(nt), k, cap, _ptr(par), _ptr(lab), _ptr(dep), _ptr(term), C.byref(n))
+        if rc != 0:
+            raise N.LasrError(rc, "lasr_prefix_tree: bad candidate list")
+        return {"parent": par[:n.value].copy(), "label": lab[:n.value].copy(), "depth": dep[:n.value].copy(), "term": term[:k].copy()}
+
+    def _cat_pcm(self, pcm_list):
+        """-> (all utterances concatenated: one device tensor if every one is, else one host array; int64 sample counts)"""
+        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
+            cat = torch.cat([x.reshape(-1).float() for x in pcm_list]).contiguous()
+        else:
+            cat = np.ascontiguousarray(np.concatenate([
+                np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
+                for x in pcm_list]))
+        return cat, np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
+
+    def _cat_feats(self, feats_list):
+        """-> (all [T', feat] blocks concatenated, device or host as _cat_pcm; int32 frame counts)"""
+        F = self.desc.feat
+        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
+            cat = torch.cat([x.reshape(-1, F).float() for x in feats_list]).contiguous()
+            nf = [x.reshape(-1, F).shape[0] for x in feats_list]
+        else:
+            arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
+            cat = np.ascontiguousarray(np.concatenate(arrs))
+            nf = [a_.shape[0] for a_ in arrs]
+        return cat, np.ascontiguousarray(np.array(nf, dtype=np.int32))
+
+    def _score(self, fn, slots_per_utt, cat, lens, cand_lists, viterbi, lattice):
+        n = len(slots_per_utt)
+        assert len(cand_lists) == n and all(len(s) == len(c) for s, c in zip(slots_per_utt, cand_lists))
+        a, p, K = self._slots([s for grp in slots_per_utt for s in grp])
+        nc = np.ascontiguousarray(np.array([len(c) for c in cand_lists], dtype=np.int32))
+        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for c in cand_lists for t in c]
+        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        loglik = np.zeros(max(K, 1), dtype=np.float64)
+        vit = np.zeros(max(K, 1), dtype=np.float64) if viterbi else None
+        trees, b, e = None, None, None
+        if lattice:      # the tree is what the library builds from the same candidates; T_i what it derives from the audio
+            trees = [self.prefix_tree(c) for c in cand_lists]
+            Ts = self._align_frames(lens, fn is self.lib.lasr_score_pcm)
+            cells = int(sum(int(t) * tr["parent"].size for t, tr in zip(Ts, trees)))
+            b, e = np.zeros(max(cells, 1), dtype=np.float32), np.zeros(max(cells, 1), dtype=np.float32)
+        self._chk(fn(self.ctx, p, n, _ptr(cat), _ptr(lens), _ptr(nc), _ptr(tok), _ptr(nt), _ptr(loglik), _ptr(vit), _ptr(b), _ptr(e)))
+        out, o, oc = [], 0, 0
+        for i in range(n):
+            k = int(nc[i])
+            r = {"loglik": loglik[o:o + k].copy()}
+            if viterbi:
+                r["viterbi"] = vit[o:o + k].copy()
+            if lattice:
+                t, nn = int(Ts[i]), int(trees[i]["parent"].size)
+                r.update(tree=trees[i], blank_lp=b[oc:oc + t * nn].reshape(t, nn).copy(), emit_lp=e[oc:oc + t * nn].reshape(t, nn).copy())
+                oc += t * nn
+            o += k
+            out.append(r)
+        return out
+
+    def score_pcm(self, slots_per_utt, pcm_list, cand_lists, viterbi=False, lattice=False):
+        """log P(candidate | audio) of every candidate of every utterance (lasr_score_pcm): each utterance is encoded once, its
+        candidates share every joint row they have a prefix in common for.  slots_per_utt[i]: one open slot per candidate of
+        utterance i (all distinct); cand_lists[i]: its candidates (non-blank ids).  -> per utterance {"loglik": float64 [k]};
+        viterbi=True adds "viterbi" [k]; lattice=True adds "tree" (prefix_tree of the candidates) and "blank_lp" / "emit_lp"
+        [T, N] float32 (emit_lp[t, v] = the emission that enters node v).  The slots are left freshly reset."""
+        assert len(pcm_list) == len(slots_per_utt)
+        cat, ns = self._cat_pcm(pcm_list)
+        return self._score(self.lib.lasr_score_pcm, slots_per_utt, cat, ns, cand_lists, viterbi, lattice)
+
+    def score_feats(self, slots_per_utt, feats_list, cand_lists, viterbi=False, lattice=False):
+        """score_pcm from stacked features (lasr_score_feats): feats_list as for transcribe_feats."""
+        assert len(feats_list) == len(slots_per_utt)
+        cat, nf = self._cat_feats(feats_list)
+        return self._score(self.lib.lasr_score_feats, slots_per_utt, cat, nf, cand_lists, viterbi, lattice)
+
+    def lattice_tree_dp(self, blank, emit, parent, viterbi=True):
+        """The tree dynamic programme alone (lasr_lattice_tree_dp) on caller-supplied lattices: blank / emit = lists of [T_i, N_i]
+        float32 arrays (emit[:, 0] is not read), parent = lists of N_i node ids (-1 at node 0, parent[v] < v, depth
+        non-decreasing).  -> per lattice {"loglik": float64 [N_i], "viterbi": float64 [N_i]}: log P(prefix_v | x) per node."""
+        n = len(blank)
+        assert n == len(emit) == len(parent) and n >= 1
+        bs = [np.asarray(x, dtype=np.float32) for x in blank]
+        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        ps = [np.asarray(x, dtype=np.int32).reshape(-1) for x in parent]
+        assert all(x.ndim == 2 and x.shape == y.shape and x.shape[1] == q.size for x, y, q in zip(bs, es, ps))
+        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
+        Nn = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
+        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
+        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        par = np.ascontiguousarray(np.concatenate(ps))
+        loglik = np.zeros(int(Nn.sum()), dtype=np.float64)
+        vit = np.zeros(int(Nn.sum()), dtype=np.float64) if viterbi else None
+        self._chk(self.lib.lasr_lattice_tree_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Nn), _ptr(par), n, _ptr(loglik), _ptr(vit)))
+        out, o = [], 0
+        for i in range(n):
+            r = {"loglik": loglik[o:o + int(Nn[i])].copy()}
+            if viterbi:
+                r["viterbi"] = vit[o:o + int(Nn[i])].copy()
+            o += int(Nn[i])
+            out.append(r)
+        return out
+
     # ------------------------------------------------------------------ op-level (tests, microbench)
     def logmel(self, pcm):
         """pcm [B, N] cuda float32 -> [B, T, n_mels]"""

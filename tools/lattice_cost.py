@@ -3,6 +3,9 @@ cfg2 (synthetic weights), the 20.65 s demo utterance with the engine's own greed
 HIP events around the call, median of 20 runs after 3 warm-up runs, and the per-stage times the engine records with profiling on
 (front-end + encoder, teacher-forced predictor, lattice blocks, dynamic programme).  The lattice blocks are dominated by the logits
 GEMM: cells x 2 J V flop, set against the f32 MFMA peak (157.3 TFLOP/s, MI355X data sheet).
+Rescoring leg: 8 candidates -- the greedy transcript y and, for j = 1..7, y with the labels from position U - 8 j onwards
+replaced by (id % (V - 3)) + 3 -- through LibreASR.score's path (lasr_align_pcm on 8 copies of the audio, no Viterbi pass) and, where
+the library has it, through LibreASR.rescore's (lasr_score_pcm: one encoder pass, the candidates' prefix tree), measured the same way.
     python tools/lattice_cost.py [f32|bf16]"""
 import json
 import os
@@ -28,25 +31,44 @@ eng.transcribe_pcm(slots[:1], [dev_pcm])
 y = eng.fetch(slots[0])[0]
 out = {"dtype": dtype, "seconds": round(len(pcm) / sr, 2), "labels": len(y), "lat_R": eng.config("lat_R")}
 eng.set_profiling(True)
-for n in (1, 8):
+
+
+def timed(call):
+    """20 calls after 3 warm-ups -> (median call and stage times in ms, the last result, the unrounded stage medians in us)"""
     ms, stages = [], []
     for rep in range(23):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        res = eng.align_pcm(slots[:n], [dev_pcm] * n, [y] * n)
+        res = call()
         e1.record()
         e1.synchronize()
         if rep >= 3:
             ms.append(e0.elapsed_time(e1))
             stages.append([eng.config(k) for k in ("lat_enc_us", "lat_pred_us", "lat_blocks_us", "lat_dp_us")])
+    st = np.median(np.asarray(stages, np.float64), axis=0)
+    return {"call_ms_median": round(float(np.median(ms)), 3), "encoder_ms": round(st[0] / 1e3, 3), "predictor_ms": round(st[1] / 1e3, 3),
+            "blocks_ms": round(st[2] / 1e3, 3), "dp_ms": round(st[3] / 1e3, 3)}, res, st
+
+
+for n in (1, 8):
+    leg, res, st = timed(lambda: eng.align_pcm(slots[:n], [dev_pcm] * n, [y] * n))
     T = (1 + len(pcm) // 160 - 10) // 8 + 1
     cells = n * T * (len(y) + 1)
-    st = np.median(np.asarray(stages, np.float64), axis=0)
     flop = cells * 2.0 * cfg["joint"] * cfg["vocab"]
-    out[f"n{n}"] = {"T": T, "cells": cells, "call_ms_median": round(float(np.median(ms)), 3),
-                    "encoder_ms": round(st[0] / 1e3, 3), "predictor_ms": round(st[1] / 1e3, 3), "blocks_ms": round(st[2] / 1e3, 3),
-                    "dp_ms": round(st[3] / 1e3, 3), "gemm_gflop": round(flop / 1e9, 1),
-                    "blocks_fraction_of_f32_mfma_peak": round(flop / (st[2] * 1e-6) / PEAK_F32_MFMA, 4) if st[2] else None,
-                    "loglik": res[0]["loglik"], "viterbi": res[0]["viterbi"]}
+    leg.update(T=T, cells=cells, gemm_gflop=round(flop / 1e9, 1),
+               blocks_fraction_of_f32_mfma_peak=round(flop / (st[2] * 1e-6) / PEAK_F32_MFMA, 4) if st[2] else None,
+               loglik=res[0]["loglik"], viterbi=res[0]["viterbi"])
+    out[f"n{n}"] = leg
+# rescoring: 8 candidates that share a prefix with the greedy transcript
+U, V = len(y), cfg["vocab"]
+cands = [list(y)] + [list(y[:max(U - 8 * j, 0)]) + [(t % (V - 3)) + 3 for t in y[max(U - 8 * j, 0):]] for j in range(1, 8)]
+leg, res, _ = timed(lambda: eng.align_pcm(slots, [dev_pcm] * 8, cands, viterbi=False))
+leg.update(rows=T * sum(len(c) + 1 for c in cands), loglik=[r["loglik"] for r in res])
+out["score_path"] = leg
+if hasattr(eng, "score_pcm"):
+    leg, res, _ = timed(lambda: eng.score_pcm([slots], [dev_pcm], [cands]))
+    leg.update(nodes=int(eng.prefix_tree(cands)["parent"].size), sum_u1=sum(len(c) + 1 for c in cands),
+               rows=T * int(eng.prefix_tree(cands)["parent"].size), loglik=[float(v) for v in res[0]["loglik"]])
+    out["rescore_path"] = leg
 eng.close()
 print(json.dumps(out))
