@@ -305,6 +305,28 @@ int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const
 int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
                      const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp);
 
+/* ---- Lattice posteriors: lasr_align_* plus the backward half of the forward-backward algorithm.  With b, e, alpha and loglik as above:
+ *   beta[T-1,U] = b[T-1,U]; beta[t,u] = logaddexp(beta[t+1,u] + b[t,u], beta[t,u+1] + e[t,u])  (a missing successor counts -inf)
+ *   occ_blank[t,u] = exp(alpha[t,u] + b[t,u] + beta[t+1,u] - loglik) (t < T-1); occ_blank[T-1,U] = 1, occ_blank[T-1,u<U] = 0
+ *   occ_emit[t,u]  = exp(alpha[t,u] + e[t,u] + beta[t,u+1] - loglik) (u < U);   occ_emit[t,U] = 0
+ * = the probability, over all alignments of the transcript, that the path takes that blank / emits label u + 1 on frame t
+ * (= d loglik / d b[t,u], d loglik / d e[t,u]); sum_t occ_emit[t,u] = 1 (u < U) and sum_u occ_blank[t,u] = 1.  Per label u = 1..U,
+ * with p(t) = occ_emit[t,u-1]: tok_mean = sum_t t p(t); tok_var = sum_t (t - tok_mean)^2 p(t); tok_peak_frame = the first t of the
+ * largest p; tok_peak = that p.  alpha, beta and the occupancies are computed in double on the device; occ_* are rounded once to f32.
+ * loglik = -inf (an impossible transcript): every occupancy 0, tok_mean -1, tok_var 0, tok_peak_frame -1, tok_peak 0; never a NaN.
+ * Arguments, preconditions, state rules and errors of lasr_align_pcm / lasr_align_feats, followed by six optional HOST outputs:
+ * occ_blank / occ_emit per utterance [T_i][U_i + 1] f32, concatenated (the layout of blank_lp / emit_lp); tok_mean, tok_var,
+ * tok_peak double [sum U_i]; tok_peak_frame int32 [sum U_i].  All six null: the call is lasr_align_*.  Otherwise alpha and beta
+ * occupy 16 bytes per cell of workspace: more than 2^24 cells in the call is LASR_EINVAL, nothing changed. */
+int lasr_align_post_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                        const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp,
+                        float* emit_lp, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame,
+                        double* tok_peak);
+int lasr_align_post_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                          const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp,
+                          float* emit_lp, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame,
+                          double* tok_peak);
+
 /* ---- N-best rescoring: one encoder pass per utterance and the lattice over a prefix tree of its candidates.
  * lasr_prefix_tree (host only: no context, no GPU) merges k >= 1 candidates -- tokens: concatenated, n_tokens[j] labels each -- into
  * a tree.  Node 0 is the empty prefix (parent -1, label -1, depth 0); every distinct non-empty prefix is one node; label[v] is the
@@ -362,6 +384,14 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
  * memory, filled before the call returns (this one synchronises): loglik [n] (required), viterbi [n], frames [sum U_i] (optional). */
 int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
                     double* loglik, double* viterbi, int32_t* frames);
+
+/* Forward-backward alone (see lasr_align_post_*), on n caller-supplied lattices: inputs and range checks as lasr_lattice_dp, and at
+ * most 2^24 cells in the call (LASR_EINVAL before anything is read).  Results in HOST memory, filled before the call returns (this
+ * one synchronises): loglik [n] (required; the forward sum, bit for bit lasr_lattice_dp's); optional: loglik_bwd [n] = beta[0,0]
+ * (loglik up to rounding), occ_blank / occ_emit [cells] f32, tok_mean / tok_var / tok_peak double and tok_peak_frame int32 [sum U_i]. */
+int lasr_lattice_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
+                      double* loglik, double* loglik_bwd, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var,
+                      int32_t* tok_peak_frame, double* tok_peak);
 
 /* The tree dynamic programme alone (see lasr_score_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
  * [T_i][N_i] f32, concatenated (emit_lp[t][0] is not read); T, n_nodes [n] and parent [sum N_i] (ids local to the lattice): HOST int32.

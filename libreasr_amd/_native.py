@@ -74,6 +74,9 @@ SYMBOLS = [
     ("lasr_align_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_align_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_lattice_dp", C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    ("lasr_align_post_pcm", C.c_int, [_P, _P, C.c_int] + [_P] * 16),
+    ("lasr_align_post_feats", C.c_int, [_P, _P, C.c_int] + [_P] * 16),
+    ("lasr_lattice_post", C.c_int, [_P, _P, _P, _P, _P, C.c_int] + [_P] * 8),
     ("lasr_prefix_tree", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("lasr_score_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_score_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -112,12 +112,24 @@ class LibreASR:
             transcript = self.lang.numericalize(transcript)
         return [int(t) for t in transcript]
 
-    def align(self, audio, transcript):
+    def _posteriors(self, r):
+        """per token of an align_pcm(posteriors=True) result: the lattice's view of where the token is, over all alignments.  Both
+        probabilities are float32 values ("peak" is tok_peak rounded as occ_emit was), so posterior <= peak <= 1 holds exactly."""
+        d = self.engine.desc
+        dt = d.stride * d.hop / d.sample_rate
+        return [{"posterior": float(r["occ_emit"][int(r["frames"][k]), k]),
+                 "time_mean_s": float(r["tok_mean"][k]) * dt, "time_std_s": float(np.sqrt(r["tok_var"][k])) * dt,
+                 "peak_time_s": float(r["tok_peak_frame"][k]) * dt, "peak": float(np.float32(r["tok_peak"][k]))}
+                for k in range(len(r["frames"]))]
+
+    def align(self, audio, transcript, posteriors=False):
         """Forced alignment of a transcript the caller already has (the teacher-forced RNN-T lattice; greedy engines).  transcript: a
         list of non-blank token ids, or text when the language object can numericalize; lists of utterances / transcripts are batched.
         -> {"score": log P(transcript | audio) summed over all alignments, "viterbi": the best alignment's log-probability,
         "tokens": [(token_id, time_s, confidence)]} with time_s the start of the 80 ms encoder frame the token falls on in the best
-        alignment and confidence the joint's probability of the token there."""
+        alignment and confidence the joint's probability of the token there.  posteriors=True adds "posteriors": per token
+        {"posterior": the probability, over ALL alignments, that the token is emitted on that frame, "time_mean_s" / "time_std_s":
+        mean and standard deviation of its emission time, "peak_time_s" / "peak": its most probable frame and the probability there}."""
         many = isinstance(audio, (list, tuple))
         batch = list(audio) if many else [audio]
         ys = [self._ids(t) for t in (transcript if many else [transcript])]
@@ -125,11 +137,14 @@ class LibreASR:
             raise ValueError("one transcript per utterance")
         slots = [self.engine.open() for _ in batch]
         try:
-            res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys)
+            res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, posteriors=bool(posteriors))
         finally:
             for s in slots:
                 self.engine.close_slot(s)
         out = [{"score": r["loglik"], "viterbi": r["viterbi"], "tokens": self._aligned(y, r["frames"], r["logps"])} for r, y in zip(res, ys)]
+        if posteriors:
+            for o, r in zip(out, res):
+                o["posteriors"] = self._posteriors(r)
         return out if many else out[0]
 
     def score(self, audio, candidates):

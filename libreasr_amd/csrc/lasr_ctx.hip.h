@@ -345,8 +345,16 @@ struct lasr_ctx {
         int* frames = nullptr; size_t frames_n = 0;       // [sum U]
         float* logps = nullptr; size_t logps_n = 0;
         unsigned* bp = nullptr; size_t bp_n = 0;          // back-pointer words of the utterances that do not fit in LDS
-        hipEvent_t ev[5] = {}; bool ev_ok = false;
-        int us[4] = {0, 0, 0, 0};     // lasr_set_profiling: front-end + encoder, predictor, lattice blocks, DP of the last call (us)
+        // posteriors (lasr_align_post_* / lasr_lattice_post, lasr_lattice_post.hip.h): null until the first such call
+        double* alpha = nullptr; size_t alpha_n = 0;      // [cells]
+        double* beta = nullptr; size_t beta_n = 0;        // [cells]
+        double* pres = nullptr; size_t pres_n = 0;        // [2 n] loglik, loglik_bwd of k_lat_ab
+        float* occ_b = nullptr; size_t occ_b_n = 0;       // [cells] each, where asked for
+        float* occ_e = nullptr; size_t occ_e_n = 0;
+        double* tstat = nullptr; size_t tstat_n = 0;      // [3][sum U] mean, variance, peak of every label's emission frame
+        int* tpeak = nullptr; size_t tpeak_n = 0;         // [sum U] the peak's frame
+        hipEvent_t ev[6] = {}; bool ev_ok = false; bool ev_post = false;   // (ev_post: the call in flight recorded ev[5])
+        int us[5] = {0, 0, 0, 0, 0};  // lasr_set_profiling: front-end + encoder, predictor, lattice blocks, DP, posteriors of the last call (us)
     } lat;
 
     // stats

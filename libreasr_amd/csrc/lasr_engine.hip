@@ -19,6 +19,7 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
 #include "lasr_lattice.hip.h"
+#include "lasr_lattice_post.hip.h"
 #include "lasr_prefix_tree.hip.h"
 #include "lasr_lattice_tree.hip.h"
 #include "lasr_weights.hip.h"
@@ -1737,10 +1738,18 @@ static int align_prologue(lasr_ctx* c, const int* slots, int n, const void* audi
     if (!audio || !lens || !loglik) return fail(c, LASR_EINVAL, "null argument");
     return lat_check_tokens(c, n, tokens, n_tokens);
 }
-int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
-                   const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+// a posterior call keeps alpha and beta of every cell: refused beyond LAT_POST_CELLS, before anything is read or changed
+static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) {
+    long long cells = 0;
+    for (int i = 0; i < n; ++i) cells += (long long)T[i] * (U[i] + 1);
+    if (cells > LAT_POST_CELLS) return fail(c, LASR_EINVAL, "posteriors of a lattice of %lld cells (at most %lld)", cells, LAT_POST_CELLS);
+    return LASR_OK;
+}
+// lasr_align_pcm; post: the posterior outputs of lasr_align_post_pcm (null: none)
+static int align_pcm_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                          const int32_t* n_tokens, const LatOut& o, const LatPostOut* post) {
     if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, loglik));
+    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, o.loglik));
     if (n == 0) return LASR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
@@ -1754,6 +1763,7 @@ int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const
         T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
         total += n_samples[i];
     }
+    if (post) RC(post_check_cells(c, Tp.data(), n_tokens, n));
     RC(ensure_T(c, T_max));
     const float* src = nullptr;
     RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
@@ -1774,12 +1784,12 @@ int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const
     stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
     RC(commit_T_rows(c, T_max));
     encode_step(c, T_max);
-    return lat_finish(c, slots, n, Tp.data(), tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp});
+    return lat_finish(c, slots, n, Tp.data(), tokens, n_tokens, o, post);
 }
-int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
-                     const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+static int align_feats_impl(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                            const int32_t* n_tokens, const LatOut& o, const LatPostOut* post) {
     if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, loglik));
+    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, o.loglik));
     if (n == 0) return LASR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
@@ -1788,6 +1798,7 @@ int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, c
         if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
         T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
     }
+    if (post) RC(post_check_cells(c, n_frames, n_tokens, n));
     RC(ensure_T(c, T_max));
     const float* src = nullptr;
     RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
@@ -1805,7 +1816,30 @@ int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, c
     stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
     RC(commit_T_rows(c, T_max));
     encode_step(c, T_max);
-    return lat_finish(c, slots, n, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp});
+    return lat_finish(c, slots, n, n_frames, tokens, n_tokens, o, post);
+}
+int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                   const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr);
+}
+int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                     const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
+    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr);
+}
+// lasr_align_* with the lattice's edge posteriors; all six posterior outputs null: lasr_align_* itself
+int lasr_align_post_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                        const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp,
+                        float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
+    const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp},
+                          lat_post_any(p) ? &p : nullptr);
+}
+int lasr_align_post_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                          const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp,
+                          float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
+    const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp},
+                            lat_post_any(p) ? &p : nullptr);
 }
 // the dynamic programme alone, on the caller's lattices (host or device); T, U and the results are host memory; blocking
 int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
@@ -1832,6 +1866,31 @@ int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, co
     if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
     return LASR_OK;
+}
+// the forward-backward programme alone, on the caller's lattices (host or device, as lasr_lattice_dp); results are host memory; blocking
+int lasr_lattice_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
+                      double* loglik_bwd, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame,
+                      double* tok_peak) {
+    if (!c) return LASR_EINVAL;
+    if (!blank_lp || !emit_lp || !T || !U || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
+    LatCall k;
+    k.n = n;
+    k.T.assign(T, T + n); k.U.assign(U, U + n); k.slot.assign(n, 0);
+    for (int i = 0; i < n; ++i)
+        if (T[i] < 1 || U[i] < 0 || U[i] > LAT_UMAX) return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d (T >= 1, 0 <= U <= %d)", i, T[i], U[i], LAT_UMAX);
+    RC(post_check_cells(c, T, U, n));
+    HIPCHK(c, hipSetDevice(c->device));
+    lasr_ctx::Lattice& w = c->lat;
+    std::vector<long long> img;
+    RC(lat_upload(c, w, k, nullptr, img));
+    const float *b = nullptr, *e = nullptr;
+    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
+    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
+    const LatPostOut p{loglik, loglik_bwd, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    RC(lat_post_launch(c, w, k, b, e, p));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return lat_post_copy(c, w, k, p);
 }
 
 // ---------------------------------------------------------------------------- n-best rescoring over a prefix tree
@@ -2989,6 +3048,7 @@ int lasr_debug_config(lasr_ctx* c, const char* key, int* value) {
         {"fe_lds_pad", c->fe_lds_pad}, {"roctx", roctx_state().push != nullptr ? 1 : 0},
         {"lat_R", LAT_R}, {"lat_umax", LAT_UMAX},      // lattice (lasr_align_*): rows per block, labels per transcript; with profiling on,
         {"lat_enc_us", c->lat.us[0]}, {"lat_pred_us", c->lat.us[1]}, {"lat_blocks_us", c->lat.us[2]}, {"lat_dp_us", c->lat.us[3]},   // the last call's stages
+        {"lat_post_us", c->lat.us[4]},                 // (alpha / beta and occupancies of the last lasr_align_* / lasr_align_post_* / lasr_score_* call: 0 unless it asked for posteriors; the lasr_lattice_* hooks record no stage times)
     };
     for (const auto& e : tab)
         if (!strcmp(e.k, key)) { *value = e.v; return LASR_OK; }

@@ -245,6 +245,13 @@ int lat_run_dp(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const float*
 }
 
 struct LatOut { double* loglik; double* viterbi; int32_t* frames; float* logps; float* blank_lp; float* emit_lp; };
+// posterior outputs (host, each optional) and the two steps that fill them: lasr_lattice_post.hip.h
+struct LatPostOut {
+    double* loglik; double* loglik_bwd; float* occ_blank; float* occ_emit;
+    double* tok_mean; double* tok_var; int32_t* tok_peak_frame; double* tok_peak;
+};
+int lat_post_launch(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const float* b, const float* e, const LatPostOut& p);
+int lat_post_copy(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const LatPostOut& p);
 
 int lat_check_tokens(lasr_ctx* c, int n, const int32_t* tokens, const int32_t* n_tokens) {
     if (!n_tokens) return fail(c, LASR_EINVAL, "null argument");
@@ -296,12 +303,18 @@ void lat_times(lasr_ctx* c, lasr_ctx::Lattice& w) {
         if (hipEventElapsedTime(&ms, w.ev[i], w.ev[i + 1]) != hipSuccess) (void)hipGetLastError();
         w.us[i] = (int)(1e3f * ms + 0.5f);
     }
+    float ms = 0.f;                                   // the posterior stage: only where this call recorded its end
+    if (w.ev_post && hipEventElapsedTime(&ms, w.ev[4], w.ev[5]) != hipSuccess) (void)hipGetLastError();
+    w.us[4] = (int)(1e3f * ms + 0.5f);
+    w.ev_post = false;
 }
 
 // Behind the front-end and the encoder of a lasr_align_* call (pe_sync holds the joint's encoder half, the listed slots are in the
 // state apply_reset left them in: predictor stepped on BOS, its joint half in pp[0]): teacher-forced predictor, lattice blocks,
-// dynamic programme, results to the host, slots back to fresh state.
-int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int32_t* tokens, const int32_t* n_tokens, const LatOut& o) {
+// dynamic programme, results to the host, slots back to fresh state.  post (lasr_align_post_*): alpha / beta and the occupancies
+// behind the dynamic programme, which then runs only for the Viterbi outputs (k_lat_ab's forward half gives loglik).
+int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int32_t* tokens, const int32_t* n_tokens, const LatOut& o,
+               const LatPostOut* post = nullptr) {
     const int M = c->M, J = c->d.joint, V = c->d.vocab;
     lasr_ctx::Lattice& w = c->lat;
     LatCall k;
@@ -332,8 +345,16 @@ int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int
     }
     lat_mark(c, w, 3);
     const bool vit = o.viterbi || o.frames || o.logps;
-    RC(lat_run_dp(c, w, k, w.b, w.e, vit, o.frames != nullptr, o.logps != nullptr));
+    if (!post || vit) RC(lat_run_dp(c, w, k, w.b, w.e, vit, o.frames != nullptr, o.logps != nullptr));
     lat_mark(c, w, 4);
+    LatPostOut po{};
+    if (post) {
+        po = *post;
+        po.loglik = vit ? nullptr : o.loglik;
+        RC(lat_post_launch(c, w, k, w.b, w.e, po));
+        lat_mark(c, w, 5);
+        w.ev_post = c->profiling && w.ev_ok;
+    }
     // ---- the slots go back to fresh state (what lasr_stream_reset(.., 1 | 2 | 4) leaves)
     RC(cmd_begin(c));
     for (int i = 0; i < n; ++i) c->hc.what[slots[i]] = 7;
@@ -342,7 +363,8 @@ int lat_finish(lasr_ctx* c, const int* slots, int n, const int* T_row, const int
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
     c->cmd_inflight = 0;
-    HIPCHK(c, hipMemcpy(o.loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (!post || vit) HIPCHK(c, hipMemcpy(o.loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (post) RC(lat_post_copy(c, w, k, po));
     if (o.viterbi) HIPCHK(c, hipMemcpy(o.viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (o.frames && k.sumU) HIPCHK(c, hipMemcpy(o.frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
     if (o.logps && k.sumU) HIPCHK(c, hipMemcpy(o.logps, w.logps, sizeof(float) * (size_t)k.sumU, hipMemcpyDeviceToHost));

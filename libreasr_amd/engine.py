@@ -376,7 +376,7 @@ class Engine:
         self._chk(self.lib.lasr_transcribe_feats(self.ctx, p, n, _ptr(cat), nf.ctypes.data_as(C.c_void_p)))
 
     # ------------------------------------------------------------------ forced alignment / transcript scoring
-    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi):
+    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi, posteriors=False):
         a, p, n = self._slots(slots)
         assert len(token_lists) == n
         toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
@@ -387,12 +387,19 @@ class Engine:
         fr = np.zeros(max(int(tok.size), 1), dtype=np.int32) if viterbi else None
         lp = np.zeros(max(int(tok.size), 1), dtype=np.float32) if viterbi else None
         b = e = None
-        if lattice:      # T_i is what the library derives from the audio: the encoder frames of the utterance
-            Ts = self._align_frames(lens, fn is self.lib.lasr_align_pcm)
+        pcm = fn is self.lib.lasr_align_pcm
+        if lattice or posteriors:      # T_i is what the library derives from the audio: the encoder frames of the utterance
+            Ts = self._align_frames(lens, pcm)
             cells = int(sum(int(t) * (int(u) + 1) for t, u in zip(Ts, U)))
+        if lattice:
             b, e = np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32)
-        self._chk(fn(self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p),
-                     U.ctypes.data_as(C.c_void_p), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e)))
+        args = (self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p),
+                U.ctypes.data_as(C.c_void_p), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e))
+        if posteriors:
+            post = self._post_buffers(cells, int(tok.size))
+            fn = self.lib.lasr_align_post_pcm if pcm else self.lib.lasr_align_post_feats
+            args += tuple(_ptr(x) for x in post)
+        self._chk(fn(*args))
         out, o, oc = [], 0, 0
         for i in range(n):
             u = int(U[i])
@@ -402,10 +409,26 @@ class Engine:
             if lattice:
                 t = int(Ts[i])
                 r.update(blank_lp=b[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(), emit_lp=e[oc:oc + t * (u + 1)].reshape(t, u + 1).copy())
-                oc += t * (u + 1)
+            if posteriors:
+                r.update(self._post_slice(post, int(Ts[i]), u, oc, o))
+            if lattice or posteriors:
+                oc += int(Ts[i]) * (u + 1)
             o += u
             out.append(r)
         return out
+
+    @staticmethod
+    def _post_buffers(cells, n_tok):
+        """host outputs of a posterior call, in the order of the C arguments: occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak"""
+        k = max(n_tok, 1)
+        return (np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32), np.zeros(k, dtype=np.float64),
+                np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64))
+
+    @staticmethod
+    def _post_slice(post, t, u, oc, o):
+        ob, oe, mean, var, pf, peak = post
+        return dict(occ_blank=ob[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(), occ_emit=oe[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(),
+                    tok_mean=mean[o:o + u].copy(), tok_var=var[o:o + u].copy(), tok_peak_frame=pf[o:o + u].copy(), tok_peak=peak[o:o + u].copy())
 
     def _align_frames(self, lens, pcm):
         d = self.desc
@@ -413,11 +436,14 @@ class Engine:
             return [int(v) for v in lens]
         return [((1 + int(v) // d.hop) - d.n_stack) // d.stride + 1 for v in lens]
 
-    def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True):
+    def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True, posteriors=False):
         """Teacher-forced RNN-T lattice of every (utterance, transcript) pair (lasr_align_pcm): pcm_list as for transcribe_pcm,
         token_lists[i] = non-blank ids.  -> per utterance {"loglik": log P(y | x) over all alignments, "viterbi": best path's score,
         "frames" / "logps": per label the encoder frame it falls on and the joint's log p there}; lattice=True adds "blank_lp" /
-        "emit_lp" [T, U + 1] float32; viterbi=False skips the alignment pass (scoring only).  The slots are left freshly reset."""
+        "emit_lp" [T, U + 1] float32; viterbi=False skips the alignment pass (scoring only).  posteriors=True (lasr_align_post_pcm)
+        adds the lattice's edge posteriors over all alignments: "occ_blank" / "occ_emit" [T, U + 1] float32 (occ_emit[t, u] = the
+        probability that label u + 1 is emitted on frame t) and per label "tok_mean" / "tok_var" (mean and variance of its emission
+        frame), "tok_peak_frame" / "tok_peak" (its most probable frame and the probability there).  The slots are left freshly reset."""
         a, p, n = self._slots(slots)
         assert len(pcm_list) == n
         if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
@@ -427,9 +453,9 @@ class Engine:
                 np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
                 for x in pcm_list]))
         ns = np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
-        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi)
+        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors)
 
-    def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True):
+    def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True, posteriors=False):
         """align_pcm from stacked features (lasr_align_feats): feats_list as for transcribe_feats."""
         a, p, n = self._slots(slots)
         assert len(feats_list) == n
@@ -442,7 +468,7 @@ class Engine:
             cat = np.ascontiguousarray(np.concatenate(arrs))
             nf = [a_.shape[0] for a_ in arrs]
         nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
-        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi)
+        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors)
 
     def lattice_dp(self, blank, emit, viterbi=True):
         """The lattice dynamic programme alone (lasr_lattice_dp) on caller-supplied lattices: blank / emit = lists of [T_i, U_i + 1]
@@ -466,6 +492,31 @@ class Engine:
             if viterbi:
                 r.update(viterbi=float(vit[i]), frames=fr[o:o + int(U[i])].copy())
             o += int(U[i])
+            out.append(r)
+        return out
+
+    def lattice_post(self, blank, emit):
+        """Forward-backward alone (lasr_lattice_post) on caller-supplied lattices, blank / emit as for lattice_dp.  -> per lattice
+        {"loglik", "loglik_bwd", "occ_blank", "occ_emit" [T, U + 1] float32, "tok_mean", "tok_var", "tok_peak_frame", "tok_peak" [U]}."""
+        n = len(blank)
+        assert n == len(emit) and n >= 1
+        bs = [np.asarray(x, dtype=np.float32) for x in blank]
+        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
+        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
+        U = np.ascontiguousarray(np.array([x.shape[1] - 1 for x in bs], dtype=np.int32))
+        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
+        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        loglik, bwd = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        post = self._post_buffers(int(b.size), int(U.sum()))
+        self._chk(self.lib.lasr_lattice_post(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(U), n, _ptr(loglik), _ptr(bwd), *[_ptr(x) for x in post]))
+        out, o, oc = [], 0, 0
+        for i in range(n):
+            t, u = int(T[i]), int(U[i])
+            r = {"loglik": float(loglik[i]), "loglik_bwd": float(bwd[i])}
+            r.update(self._post_slice(post, t, u, oc, o))
+            o += u
+            oc += t * (u + 1)
             out.append(r)
         return out
 

@@ -6,6 +6,8 @@ GEMM: cells x 2 J V flop, set against the f32 MFMA peak (157.3 TFLOP/s, MI355X d
 Rescoring leg: 8 candidates -- the greedy transcript y and, for j = 1..7, y with the labels from position U - 8 j onwards
 replaced by (id % (V - 3)) + 3 -- through LibreASR.score's path (lasr_align_pcm on 8 copies of the audio, no Viterbi pass) and, where
 the library has it, through LibreASR.rescore's (lasr_score_pcm: one encoder pass, the candidates' prefix tree), measured the same way.
+Posterior leg: the n = 1 and n = 8 calls again with posteriors=True (lasr_align_post_pcm: alpha / beta and the occupancies
+behind the same stages), beside the plain legs of the same process; post_ms is the added stage, to be set against dp_ms.
     python tools/lattice_cost.py [f32|bf16]"""
 import json
 import os
@@ -44,10 +46,10 @@ def timed(call):
         e1.synchronize()
         if rep >= 3:
             ms.append(e0.elapsed_time(e1))
-            stages.append([eng.config(k) for k in ("lat_enc_us", "lat_pred_us", "lat_blocks_us", "lat_dp_us")])
+            stages.append([eng.config(k) for k in ("lat_enc_us", "lat_pred_us", "lat_blocks_us", "lat_dp_us", "lat_post_us")])
     st = np.median(np.asarray(stages, np.float64), axis=0)
     return {"call_ms_median": round(float(np.median(ms)), 3), "encoder_ms": round(st[0] / 1e3, 3), "predictor_ms": round(st[1] / 1e3, 3),
-            "blocks_ms": round(st[2] / 1e3, 3), "dp_ms": round(st[3] / 1e3, 3)}, res, st
+            "blocks_ms": round(st[2] / 1e3, 3), "dp_ms": round(st[3] / 1e3, 3), "post_ms": round(st[4] / 1e3, 3)}, res, st
 
 
 for n in (1, 8):
@@ -59,6 +61,10 @@ for n in (1, 8):
                blocks_fraction_of_f32_mfma_peak=round(flop / (st[2] * 1e-6) / PEAK_F32_MFMA, 4) if st[2] else None,
                loglik=res[0]["loglik"], viterbi=res[0]["viterbi"])
     out[f"n{n}"] = leg
+    leg, res, st = timed(lambda: eng.align_pcm(slots[:n], [dev_pcm] * n, [y] * n, posteriors=True))
+    leg.update(post_over_dp=round(st[4] / st[3], 3) if st[3] else None, loglik=res[0]["loglik"],
+               mean_time_std_frames=round(float(np.sqrt(res[0]["tok_var"]).mean()), 4) if len(y) else None)
+    out[f"n{n}_post"] = leg
 # rescoring: 8 candidates that share a prefix with the greedy transcript
 U, V = len(y), cfg["vocab"]
 cands = [list(y)] + [list(y[:max(U - 8 * j, 0)]) + [(t % (V - 3)) + 3 for t in y[max(U - 8 * j, 0):]] for j in range(1, 8)]
