@@ -327,6 +327,43 @@ int lasr_align_post_feats(lasr_ctx* c, const int* slots, int n, const float* fea
                           float* emit_lp, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame,
                           double* tok_peak);
 
+/* ---- Banded forced alignment: the lattice restricted to w labels per frame, so that joint, dynamic programme and workspace grow
+ * with T w instead of T (U + 1) and the transcript may have up to 32767 labels.
+ * Per utterance, with a requested width band >= 1: w = U + 1 where T == 1, else min(band, U + 1); w <= 1536.  Frame t owns the columns
+ * [lo[t], lo[t] + w).  Windows are VALID when lo[0] == 0, lo[T-1] == U + 1 - w, lo is non-decreasing and 0 <= lo[t] <= U + 1 - w: every
+ * window cell is a lattice cell, (0,0) and (T-1,U) are inside.  b and e are lasr_align_*'s terms at the window cells and count -inf
+ * outside; alpha, loglik, viterbi (with its tie rule), frames and logps are lasr_align_*'s recursions on that lattice (a predecessor
+ * outside its frame's window counts -inf; never a NaN).  loglik <= the full lattice's; with w == U + 1 everything is the full lattice's.
+ * Windows that do not overlap leave no path: loglik = viterbi = -inf, frames all -1, logps 0, touch 0.
+ * BAND LAYOUT of a lattice array: per utterance [T_i][w_i], cell = off_i + t w_i + k holds u = lo[t] + k; emit_lp at u == U is 0.
+ *
+ * lasr_band_windows (host only: no context, no GPU; integer arithmetic only).  frames == NULL: the LINEAR windows
+ * lo_out[t] = floor(t (U + 1 - w) / (T - 1)) (T == 1: 0), *touch = 0, lo_cur is not read.  Otherwise frames [U] is a best path found
+ * inside the valid windows lo_cur [T], and with c(t) = #{u : frames[u] < t} (c(T) = U; the path occupies columns c(t)..c(t+1) on
+ * frame t) the RECENTRED windows are lo_out[t] = clamp(floor((c(t) + c(t+1)) / 2) - floor(w / 2), 0, U + 1 - w), then lo_out[0] = 0
+ * and lo_out[T-1] = U + 1 - w (always valid; lo_out may be lo_cur), and *touch (optional) = 1 iff some frame has lo_cur[t] > 0 and
+ * c(t) == lo_cur[t], or lo_cur[t] + w < U + 1 and c(t+1) == lo_cur[t] + w - 1: the path ran along a window edge that is not the
+ * lattice's own.  touch == 0 is evidence that the band did not constrain the path, not a proof that it is the full lattice's best.
+ * LASR_EINVAL: T < 1, U < 0, band < 1, lo_out null, frames given and lo_cur null or not valid, frames decreasing or outside [0, T). */
+int lasr_band_windows(int T, int U, int band, const int32_t* frames, const int32_t* lo_cur, int32_t* lo_out, int* touch);
+
+/* lasr_align_band_*: every argument, precondition, state rule and error of lasr_align_pcm / lasr_align_feats, except that
+ * n_tokens[i] <= 32767, and in addition: band >= 1, max_passes >= 1, lo_in (HOST, [sum T_i], T_i = the encoder frames of utterance i;
+ * NULL: linear windows) the windows of the first pass.  The front-end, the encoder and the teacher-forced predictor run once.  A pass
+ * evaluates the band cells of all utterances under the current windows and runs the banded dynamic programme.  With max_passes == 1
+ * the Viterbi half runs only when viterbi, frames, logps or touch is asked for.  With max_passes > 1 the best paths come to the host
+ * after every pass, and windows and touch are recomputed by lasr_band_windows' routine (an utterance without a path keeps its
+ * windows, touch 0); the loop ends when no utterance touches, when no window changed, or at max_passes.  Outputs are the last
+ * pass's: blank_lp / emit_lp in band layout, and optionally (HOST) lo_out [sum T_i] the windows of that pass, passes [n] the passes
+ * run (the same for the whole call), touch [n].  LASR_EINVAL, nothing changed: as lasr_align_*, band < 1, max_passes < 1, a w beyond
+ * 1536 (a single-frame utterance needs U + 1), lo_in not valid, 2^31 band cells or more. */
+int lasr_align_band_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                        const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                        int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch);
+int lasr_align_band_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                          const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                          int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch);
+
 /* ---- N-best rescoring: one encoder pass per utterance and the lattice over a prefix tree of its candidates.
  * lasr_prefix_tree (host only: no context, no GPU) merges k >= 1 candidates -- tokens: concatenated, n_tokens[j] labels each -- into
  * a tree.  Node 0 is the empty prefix (parent -1, label -1, depth 0); every distinct non-empty prefix is one node; label[v] is the
@@ -384,6 +421,15 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
  * memory, filled before the call returns (this one synchronises): loglik [n] (required), viterbi [n], frames [sum U_i] (optional). */
 int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
                     double* loglik, double* viterbi, int32_t* frames);
+
+/* The banded dynamic programme alone (see lasr_align_band_*), on n caller-supplied band lattices: blank_lp / emit_lp host or device,
+ * per lattice [T_i][W_i] f32 in band layout, concatenated (emit_lp at u == U is not read); T, U, W: HOST int32 [n]; lo: HOST int32
+ * [sum T_i], valid windows of width W_i.  W_i must be an effective width: 1 <= W <= min(U + 1, 1536), and W == U + 1 where T == 1;
+ * T >= 1, 0 <= U <= 32767, fewer than 2^31 cells in the call; LASR_EINVAL otherwise.  Results in HOST memory, filled before the call
+ * returns (this one synchronises): loglik [n] (required), viterbi [n], frames [sum U_i] (optional).  With W == U + 1 the results
+ * are lasr_lattice_dp's bit for bit. */
+int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                         const int32_t* lo, int n, double* loglik, double* viterbi, int32_t* frames);
 
 /* Forward-backward alone (see lasr_align_post_*), on n caller-supplied lattices: inputs and range checks as lasr_lattice_dp, and at
  * most 2^24 cells in the call (LASR_EINVAL before anything is read).  Results in HOST memory, filled before the call returns (this

@@ -122,14 +122,21 @@ class LibreASR:
                  "peak_time_s": float(r["tok_peak_frame"][k]) * dt, "peak": float(np.float32(r["tok_peak"][k]))}
                 for k in range(len(r["frames"]))]
 
-    def align(self, audio, transcript, posteriors=False):
+    def align(self, audio, transcript, posteriors=False, band=None, max_passes=4):
         """Forced alignment of a transcript the caller already has (the teacher-forced RNN-T lattice; greedy engines).  transcript: a
         list of non-blank token ids, or text when the language object can numericalize; lists of utterances / transcripts are batched.
         -> {"score": log P(transcript | audio) summed over all alignments, "viterbi": the best alignment's log-probability,
         "tokens": [(token_id, time_s, confidence)]} with time_s the start of the 80 ms encoder frame the token falls on in the best
         alignment and confidence the joint's probability of the token there.  posteriors=True adds "posteriors": per token
         {"posterior": the probability, over ALL alignments, that the token is emitted on that frame, "time_mean_s" / "time_std_s":
-        mean and standard deviation of its emission time, "peak_time_s" / "peak": its most probable frame and the probability there}."""
+        mean and standard deviation of its emission time, "peak_time_s" / "peak": its most probable frame and the probability there}.
+        band=W restricts the lattice to W labels per frame (lasr_align_band_pcm: cost linear in the audio's length, transcripts of
+        up to 32767 labels), the windows recentred on the best path for up to max_passes passes; score and viterbi are then those of
+        the band (score <= the full lattice's), and "band": {"width": the effective width, "passes": passes run, "touch": whether the
+        last pass's path still ran along a window edge -- False is evidence, not proof, that the band did not constrain it} is added.
+        band with posteriors=True raises ValueError (banded posteriors are not built)."""
+        if band is not None and posteriors:
+            raise ValueError("align: posteriors=True is not available with a band")
         many = isinstance(audio, (list, tuple))
         batch = list(audio) if many else [audio]
         ys = [self._ids(t) for t in (transcript if many else [transcript])]
@@ -137,7 +144,10 @@ class LibreASR:
             raise ValueError("one transcript per utterance")
         slots = [self.engine.open() for _ in batch]
         try:
-            res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, posteriors=bool(posteriors))
+            if band is None:
+                res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, posteriors=bool(posteriors))
+            else:
+                res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, band=int(band), max_passes=int(max_passes))
         finally:
             for s in slots:
                 self.engine.close_slot(s)
@@ -145,6 +155,9 @@ class LibreASR:
         if posteriors:
             for o, r in zip(out, res):
                 o["posteriors"] = self._posteriors(r)
+        if band is not None:
+            for o, r in zip(out, res):
+                o["band"] = {"width": int(r["width"]), "passes": int(r["passes"]), "touch": bool(r["touch"])}
         return out if many else out[0]
 
     def score(self, audio, candidates):

@@ -1727,16 +1727,27 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
 }
 
 // ---------------------------------------------------------------------------- teacher-forced lattice
+// The banded lattice is compiled at the END of this unit -- lasr_lattice_band.hip.h and its entry points follow the
+// last function below, so nothing that was here before moves -- and lasr_align_*'s two bodies reach it through these declarations.
+namespace lasr {
+constexpr int LAT_BAND_WMAX = 1536;    // window width: four diagonals of doubles (48 KB) + 16 KB of back-pointers = 64 KB of LDS
+constexpr int LAT_BAND_UMAX = 32767;   // labels per transcript of a banded call (the teacher-forced predictor keeps (U + 1) rows x J)
+}
+namespace {
+struct LatBandIO;
+int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io);
+int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io);
+}
 // common head of lasr_align_*: a greedy, idle context, open slots, a valid transcript per utterance -- nothing has changed when it fails
 static int align_prologue(lasr_ctx* c, const int* slots, int n, const void* audio, const void* lens, const int32_t* tokens,
-                          const int32_t* n_tokens, const double* loglik) {
+                          const int32_t* n_tokens, const double* loglik, int umax = LAT_UMAX) {
     if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_align_*: greedy contexts only (beam = %d)", c->W);
     RC(flush_lazy(c));
     RC(require_idle(c));
     RC(check_slots(c, slots, n, true));
     if (n == 0) return LASR_OK;
     if (!audio || !lens || !loglik) return fail(c, LASR_EINVAL, "null argument");
-    return lat_check_tokens(c, n, tokens, n_tokens);
+    return lat_check_tokens(c, n, tokens, n_tokens, umax);
 }
 // a posterior call keeps alpha and beta of every cell: refused beyond LAT_POST_CELLS, before anything is read or changed
 static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) {
@@ -1745,11 +1756,11 @@ static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) 
     if (cells > LAT_POST_CELLS) return fail(c, LASR_EINVAL, "posteriors of a lattice of %lld cells (at most %lld)", cells, LAT_POST_CELLS);
     return LASR_OK;
 }
-// lasr_align_pcm; post: the posterior outputs of lasr_align_post_pcm (null: none)
+// lasr_align_pcm; post: the posterior outputs of lasr_align_post_pcm (null: none); band: lasr_align_band_pcm (null: the full lattice)
 static int align_pcm_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
-                          const int32_t* n_tokens, const LatOut& o, const LatPostOut* post) {
+                          const int32_t* n_tokens, const LatOut& o, const LatPostOut* post, const LatBandIO* band = nullptr) {
     if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, o.loglik));
+    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, o.loglik, band ? LAT_BAND_UMAX : LAT_UMAX));
     if (n == 0) return LASR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
@@ -1764,6 +1775,7 @@ static int align_pcm_impl(lasr_ctx* c, const int* slots, int n, const float* pcm
         total += n_samples[i];
     }
     if (post) RC(post_check_cells(c, Tp.data(), n_tokens, n));
+    if (band) RC(lat_band_plan(c, Tp.data(), n_tokens, n, *band));
     RC(ensure_T(c, T_max));
     const float* src = nullptr;
     RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
@@ -1784,12 +1796,13 @@ static int align_pcm_impl(lasr_ctx* c, const int* slots, int n, const float* pcm
     stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
     RC(commit_T_rows(c, T_max));
     encode_step(c, T_max);
+    if (band) return lat_finish_band(c, slots, n, tokens, o, *band);
     return lat_finish(c, slots, n, Tp.data(), tokens, n_tokens, o, post);
 }
 static int align_feats_impl(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
-                            const int32_t* n_tokens, const LatOut& o, const LatPostOut* post) {
+                            const int32_t* n_tokens, const LatOut& o, const LatPostOut* post, const LatBandIO* band = nullptr) {
     if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, o.loglik));
+    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, o.loglik, band ? LAT_BAND_UMAX : LAT_UMAX));
     if (n == 0) return LASR_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const lasr_model_desc& d = c->d;
@@ -1799,6 +1812,7 @@ static int align_feats_impl(lasr_ctx* c, const int* slots, int n, const float* f
         T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
     }
     if (post) RC(post_check_cells(c, n_frames, n_tokens, n));
+    if (band) RC(lat_band_plan(c, n_frames, n_tokens, n, *band));
     RC(ensure_T(c, T_max));
     const float* src = nullptr;
     RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
@@ -1816,6 +1830,7 @@ static int align_feats_impl(lasr_ctx* c, const int* slots, int n, const float* f
     stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
     RC(commit_T_rows(c, T_max));
     encode_step(c, T_max);
+    if (band) return lat_finish_band(c, slots, n, tokens, o, *band);
     return lat_finish(c, slots, n, n_frames, tokens, n_tokens, o, post);
 }
 int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
@@ -3048,6 +3063,7 @@ int lasr_debug_config(lasr_ctx* c, const char* key, int* value) {
         {"fe_lds_pad", c->fe_lds_pad}, {"roctx", roctx_state().push != nullptr ? 1 : 0},
         {"lat_R", LAT_R}, {"lat_umax", LAT_UMAX},      // lattice (lasr_align_*): rows per block, labels per transcript; with profiling on,
         {"lat_enc_us", c->lat.us[0]}, {"lat_pred_us", c->lat.us[1]}, {"lat_blocks_us", c->lat.us[2]}, {"lat_dp_us", c->lat.us[3]},   // the last call's stages
+        {"lat_band_wmax", LAT_BAND_WMAX}, {"lat_band_umax", LAT_BAND_UMAX}, {"lat_bp_words", LAT_BP_WORDS},   // banded lattice (lasr_align_band_*): widest window, labels per transcript; back-pointer words a workgroup keeps in LDS
         {"lat_post_us", c->lat.us[4]},                 // (alpha / beta and occupancies of the last lasr_align_* / lasr_align_post_* / lasr_score_* call: 0 unless it asked for posteriors; the lasr_lattice_* hooks record no stage times)
     };
     for (const auto& e : tab)
@@ -3092,3 +3108,56 @@ int lasr_bench_cell(lasr_ctx* c, int layer, int iters, double* us) {
 }  // extern "C"
 
 #include "lasr_front.hip.h"
+
+// ---------------------------------------------------------------------------- banded lattice
+#include "lasr_band_windows.hip.h"
+#include "lasr_lattice_band.hip.h"
+int lasr_band_windows(int T, int U, int band, const int32_t* frames, const int32_t* lo_cur, int32_t* lo_out, int* touch) {
+    return lasr_bw::band_windows(T, U, band, frames, lo_cur, lo_out, touch);
+}
+int lasr_align_band_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                        const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                        int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch) {
+    LatBandCall k;
+    const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
+    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io);
+}
+int lasr_align_band_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                          const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                          int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch) {
+    LatBandCall k;
+    const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
+    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io);
+}
+// the banded dynamic programme alone, on the caller's band lattices (host or device); T, U, W, lo and the results are host memory; blocking
+int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                         const int32_t* lo, int n, double* loglik, double* viterbi, int32_t* frames) {
+    if (!c) return LASR_EINVAL;
+    if (!blank_lp || !emit_lp || !T || !U || !W || !lo || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
+    LatBandCall k;
+    k.n = n;
+    k.T.assign(T, T + n); k.U.assign(U, U + n); k.W.assign(W, W + n); k.slot.assign(n, 0);
+    for (int i = 0; i < n; ++i)
+        if (T[i] < 1 || U[i] < 0 || U[i] > LAT_BAND_UMAX || W[i] < 1 || W[i] > std::min(U[i] + 1, LAT_BAND_WMAX) || (T[i] == 1 && W[i] != U[i] + 1))
+            return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d, W = %d (T >= 1, 0 <= U <= %d, 1 <= W <= min(U + 1, %d), W = U + 1 where T = 1)",
+                        i, T[i], U[i], W[i], LAT_BAND_UMAX, LAT_BAND_WMAX);
+    RC(lat_band_layout(c, k));
+    k.lo.assign(lo, lo + k.sumT);
+    for (int i = 0; i < n; ++i)
+        if (!lasr_bw::valid(T[i], U[i], W[i], lo + k.lo_off[i])) return fail(c, LASR_EINVAL, "lattice %d: lo is not a valid set of windows of width %d", i, W[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    lasr_ctx::Lattice& w = c->lat;
+    std::vector<long long> img;
+    RC(lat_band_upload(c, w, k, nullptr, img));
+    const float *b = nullptr, *e = nullptr;
+    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
+    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
+    const bool vit = viterbi || frames;
+    RC(lat_band_run_dp(c, w, k, b, e, vit, frames != nullptr, false));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
+    return LASR_OK;
+}

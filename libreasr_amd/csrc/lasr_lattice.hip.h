@@ -253,11 +253,11 @@ struct LatPostOut {
 int lat_post_launch(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const float* b, const float* e, const LatPostOut& p);
 int lat_post_copy(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const LatPostOut& p);
 
-int lat_check_tokens(lasr_ctx* c, int n, const int32_t* tokens, const int32_t* n_tokens) {
+int lat_check_tokens(lasr_ctx* c, int n, const int32_t* tokens, const int32_t* n_tokens, int umax = LAT_UMAX) {
     if (!n_tokens) return fail(c, LASR_EINVAL, "null argument");
     long long at = 0;
     for (int i = 0; i < n; ++i) {
-        if (n_tokens[i] < 0 || n_tokens[i] > LAT_UMAX) return fail(c, LASR_EINVAL, "transcript %d has %d labels (0..%d)", i, n_tokens[i], LAT_UMAX);
+        if (n_tokens[i] < 0 || n_tokens[i] > umax) return fail(c, LASR_EINVAL, "transcript %d has %d labels (0..%d)", i, n_tokens[i], umax);
         if (n_tokens[i] > 0 && !tokens) return fail(c, LASR_EINVAL, "null argument");
         for (int u = 0; u < n_tokens[i]; ++u) {
             const int y = tokens[at + u];

@@ -376,7 +376,11 @@ class Engine:
         self._chk(self.lib.lasr_transcribe_feats(self.ctx, p, n, _ptr(cat), nf.ctypes.data_as(C.c_void_p)))
 
     # ------------------------------------------------------------------ forced alignment / transcript scoring
-    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi, posteriors=False):
+    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi, posteriors=False, band=None, max_passes=1, windows=None):
+        if band is not None:
+            if posteriors:
+                raise ValueError("posteriors are not available with a band")
+            return self._align_band(fn is self.lib.lasr_align_pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows)
         a, p, n = self._slots(slots)
         assert len(token_lists) == n
         toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
@@ -417,6 +421,100 @@ class Engine:
             out.append(r)
         return out
 
+    def _align_band(self, pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows):
+        """lasr_align_band_pcm / _feats: _align's dicts with the lattice arrays [T, w] in band layout, and "lo", "width", "passes", "touch"."""
+        a, p, n = self._slots(slots)
+        assert len(token_lists) == n
+        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+        U = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        Ts = self._align_frames(lens, pcm)
+        W = [int(u) + 1 if int(t) == 1 else min(int(band), int(u) + 1) for t, u in zip(Ts, U)]
+        cells = int(sum(int(t) * w for t, w in zip(Ts, W)))
+        loglik = np.zeros(n, dtype=np.float64)
+        vit = np.zeros(n, dtype=np.float64) if viterbi else None
+        fr = np.zeros(max(int(tok.size), 1), dtype=np.int32) if viterbi else None
+        lp = np.zeros(max(int(tok.size), 1), dtype=np.float32) if viterbi else None
+        b = np.zeros(max(cells, 1), dtype=np.float32) if lattice else None
+        e = np.zeros(max(cells, 1), dtype=np.float32) if lattice else None
+        lo_in = None
+        if windows is not None:
+            assert len(windows) == n
+            lo_in = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in windows]))
+            if lo_in.size != sum(Ts):
+                raise N.LasrError(N.LASR_EINVAL, "windows: one start per encoder frame of every utterance")
+        lo = np.zeros(max(int(sum(Ts)), 1), dtype=np.int32)
+        passes, touch = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        fn = self.lib.lasr_align_band_pcm if pcm else self.lib.lasr_align_band_feats
+        self._chk(fn(self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p), U.ctypes.data_as(C.c_void_p),
+                     int(band), int(max_passes), _ptr(lo_in), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e), _ptr(lo),
+                     _ptr(passes), _ptr(touch)))
+        out, o, oc, ot = [], 0, 0, 0
+        for i in range(n):
+            u, t, w = int(U[i]), int(Ts[i]), W[i]
+            r = {"loglik": float(loglik[i])}
+            if viterbi:
+                r.update(viterbi=float(vit[i]), frames=fr[o:o + u].copy(), logps=lp[o:o + u].copy())
+            if lattice:
+                r.update(blank_lp=b[oc:oc + t * w].reshape(t, w).copy(), emit_lp=e[oc:oc + t * w].reshape(t, w).copy())
+            r.update(lo=lo[ot:ot + t].copy(), width=w, passes=int(passes[i]), touch=int(touch[i]))
+            o += u
+            oc += t * w
+            ot += t
+            out.append(r)
+        return out
+
+    @staticmethod
+    def band_windows(T, U, band, frames=None, lo=None):
+        """The window arithmetic of the banded lattice (lasr_band_windows; host only, no context: callable on the class).  frames=None: the linear windows of T frames,
+        U labels and the requested width band; otherwise the windows recentred on the best path `frames` [U] that was found inside
+        the windows `lo` [T].  -> (lo int32 [T], touch: 1 iff that path ran along an edge of `lo` that is not the lattice's own)."""
+        out = np.zeros(max(int(T), 1), dtype=np.int32)
+        touch = C.c_int(0)
+        fr = cur = None
+        if frames is not None:
+            fr = np.ascontiguousarray(np.asarray(frames, dtype=np.int32).reshape(-1))
+            if fr.size != int(U) or lo is None:
+                raise N.LasrError(N.LASR_EINVAL, "lasr_band_windows: frames needs U entries and the windows it was found in")
+            fr = np.concatenate([fr, np.zeros(1, np.int32)])          # (never null, so U = 0 still means "recentre")
+            cur = np.ascontiguousarray(np.asarray(lo, dtype=np.int32).reshape(-1))
+            if cur.size != int(T):
+                raise N.LasrError(N.LASR_EINVAL, "lasr_band_windows: lo needs T entries")
+        rc = N.lib().lasr_band_windows(int(T), int(U), int(band), _ptr(fr), _ptr(cur), _ptr(out), C.byref(touch))
+        if rc != 0:
+            raise N.LasrError(rc, "lasr_band_windows: bad argument")
+        return out[:int(T)].copy(), int(touch.value)
+
+    def lattice_band_dp(self, blank, emit, lo, U, viterbi=True):
+        """The banded dynamic programme alone (lasr_lattice_band_dp) on caller-supplied band lattices: blank / emit = lists of
+        [T_i, w_i] float32 arrays in band layout (row t holds the columns lo_i[t] .. lo_i[t] + w_i - 1), lo = their window starts,
+        U = their label counts.  -> per lattice {"loglik", "viterbi", "frames"}."""
+        n = len(blank)
+        assert n == len(emit) == len(lo) == len(U) and n >= 1
+        bs = [np.asarray(x, dtype=np.float32) for x in blank]
+        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
+        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
+        W = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
+        Us = np.ascontiguousarray(np.array([int(u) for u in U], dtype=np.int32))
+        los = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in lo]))
+        assert los.size == int(T.sum())
+        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
+        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        loglik = np.zeros(n, dtype=np.float64)
+        vit = np.zeros(n, dtype=np.float64) if viterbi else None
+        fr = np.zeros(max(int(Us.sum()), 1), dtype=np.int32) if viterbi else None
+        self._chk(self.lib.lasr_lattice_band_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Us), _ptr(W), _ptr(los), n, _ptr(loglik), _ptr(vit),
+                                                _ptr(fr)))
+        out, o = [], 0
+        for i in range(n):
+            r = {"loglik": float(loglik[i])}
+            if viterbi:
+                r.update(viterbi=float(vit[i]), frames=fr[o:o + int(Us[i])].copy())
+            o += int(Us[i])
+            out.append(r)
+        return out
+
     @staticmethod
     def _post_buffers(cells, n_tok):
         """host outputs of a posterior call, in the order of the C arguments: occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak"""
@@ -436,14 +534,18 @@ class Engine:
             return [int(v) for v in lens]
         return [((1 + int(v) // d.hop) - d.n_stack) // d.stride + 1 for v in lens]
 
-    def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True, posteriors=False):
+    def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True, posteriors=False, band=None, max_passes=1, windows=None):
         """Teacher-forced RNN-T lattice of every (utterance, transcript) pair (lasr_align_pcm): pcm_list as for transcribe_pcm,
         token_lists[i] = non-blank ids.  -> per utterance {"loglik": log P(y | x) over all alignments, "viterbi": best path's score,
         "frames" / "logps": per label the encoder frame it falls on and the joint's log p there}; lattice=True adds "blank_lp" /
         "emit_lp" [T, U + 1] float32; viterbi=False skips the alignment pass (scoring only).  posteriors=True (lasr_align_post_pcm)
         adds the lattice's edge posteriors over all alignments: "occ_blank" / "occ_emit" [T, U + 1] float32 (occ_emit[t, u] = the
         probability that label u + 1 is emitted on frame t) and per label "tok_mean" / "tok_var" (mean and variance of its emission
-        frame), "tok_peak_frame" / "tok_peak" (its most probable frame and the probability there).  The slots are left freshly reset."""
+        frame), "tok_peak_frame" / "tok_peak" (its most probable frame and the probability there).  The slots are left freshly reset.
+        band=W (lasr_align_band_pcm): the lattice restricted to W labels per frame -- w = min(W, U + 1) (U + 1 on a single frame) --
+        starting from `windows` (per utterance the T window starts; None: linear) and recentred on the best path for up to max_passes
+        passes; transcripts of up to 32767 labels.  The dict then also has "lo" int32 [T] (the last pass's windows), "width",
+        "passes" and "touch", and the lattice arrays are [T, w] in band layout (row t holds the columns lo[t] .. lo[t] + w - 1)."""
         a, p, n = self._slots(slots)
         assert len(pcm_list) == n
         if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
@@ -453,10 +555,10 @@ class Engine:
                 np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
                 for x in pcm_list]))
         ns = np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
-        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors)
+        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
 
-    def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True, posteriors=False):
-        """align_pcm from stacked features (lasr_align_feats): feats_list as for transcribe_feats."""
+    def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True, posteriors=False, band=None, max_passes=1, windows=None):
+        """align_pcm from stacked features (lasr_align_feats; with a band lasr_align_band_feats): feats_list as for transcribe_feats."""
         a, p, n = self._slots(slots)
         assert len(feats_list) == n
         F = self.desc.feat
@@ -468,7 +570,7 @@ class Engine:
             cat = np.ascontiguousarray(np.concatenate(arrs))
             nf = [a_.shape[0] for a_ in arrs]
         nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
-        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors)
+        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
 
     def lattice_dp(self, blank, emit, viterbi=True):
         """The lattice dynamic programme alone (lasr_lattice_dp) on caller-supplied lattices: blank / emit = lists of [T_i, U_i + 1]

@@ -8,6 +8,10 @@ replaced by (id % (V - 3)) + 3 -- through LibreASR.score's path (lasr_align_pcm 
 the library has it, through LibreASR.rescore's (lasr_score_pcm: one encoder pass, the candidates' prefix tree), measured the same way.
 Posterior leg: the n = 1 and n = 8 calls again with posteriors=True (lasr_align_post_pcm: alpha / beta and the occupancies
 behind the same stages), beside the plain legs of the same process; post_ms is the added stage, to be set against dp_ms.
+Banded leg: the utterance tiled 4x (82.6 s) with the engine's own greedy transcript of that audio, n = 1:
+lasr_align_pcm on the full lattice beside lasr_align_band_pcm with band = 64 at max_passes 1 and 4 -- stage times (with several
+passes blocks_ms runs from the end of the predictor to the end of the last pass's blocks, dp_ms is the last pass's), cells, passes,
+touch, and how far the banded viterbi score and frames are from the full lattice's.
     python tools/lattice_cost.py [f32|bf16]"""
 import json
 import os
@@ -76,5 +80,27 @@ if hasattr(eng, "score_pcm"):
     leg.update(nodes=int(eng.prefix_tree(cands)["parent"].size), sum_u1=sum(len(c) + 1 for c in cands),
                rows=T * int(eng.prefix_tree(cands)["parent"].size), loglik=[float(v) for v in res[0]["loglik"]])
     out["rescore_path"] = leg
+# banded alignment of long audio
+if hasattr(eng, "lattice_band_dp"):
+    long_pcm = torch.cat([dev_pcm] * 4)
+    eng.transcribe_pcm(slots[:1], [long_pcm])
+    yl = eng.fetch(slots[0])[0]
+    Tl = (1 + 4 * len(pcm) // 160 - 10) // 8 + 1
+    out["long"] = {"seconds": round(4 * len(pcm) / sr, 2), "labels": len(yl), "T": Tl}
+    full = None
+    if len(yl) <= eng.config("lat_umax"):
+        leg, res, _ = timed(lambda: eng.align_pcm(slots[:1], [long_pcm], [yl]))
+        full = res[0]
+        leg.update(cells=Tl * (len(yl) + 1), loglik=full["loglik"], viterbi=full["viterbi"])
+        out["long_full"] = leg
+    for mp in (1, 4):
+        leg, res, _ = timed(lambda: eng.align_pcm(slots[:1], [long_pcm], [yl], band=64, max_passes=mp))
+        r = res[0]
+        leg.update(cells=Tl * r["width"], width=r["width"], passes=r["passes"], touch=r["touch"], loglik=r["loglik"], viterbi=r["viterbi"])
+        if full is not None:
+            d = np.abs(np.asarray(r["frames"], np.int64) - np.asarray(full["frames"], np.int64))
+            leg.update(viterbi_minus_full=r["viterbi"] - full["viterbi"], loglik_minus_full=r["loglik"] - full["loglik"],
+                       frames_differ=int((d > 0).sum()), frames_max_abs_diff=int(d.max()) if d.size else 0)
+        out[f"long_band64_p{mp}"] = leg
 eng.close()
 print(json.dumps(out))
