@@ -518,6 +518,12 @@ __device__ __forceinline__ bool any16(bool flag, int lane) {
     return (__ballot(flag && lane < 16) != 0ull);   // wave-uniform OR over lanes 0..15
 }
 
+// Row of a per-token table for a token id that lives in device memory.  Every id the selection kernels store is in [0, V)
+// (lasr_kernels.hip.h: amax_before / amax_index); this is the second, independent layer: an id outside [0, V), however it got
+// there, reads row 0 and never memory outside the table.  One unsigned compare + select on the integer the gather loads anyway.
+// (Used by every gather indexed by a device-resident token: EpiLSTM, EpiNBRC, EpiLSTMw, EpiNBRCw and k_lm_cell_q.)
+__device__ __forceinline__ size_t tab_row(int token, int V) { return (unsigned)token < (unsigned)V ? (size_t)token : (size_t)0; }
+
 // ---- LSTM cell (torch gate order i,f,g,o; custom_rnn.py:172, haste/lstm.py:34-68) + BN(eval) fold.
 // h ping-pongs between two buffers (every workgroup reads all of h while others write their units);
 // rows that do not advance are carried to the other buffer by the workgroup that owns the units.
@@ -529,6 +535,7 @@ struct LstmArgs {
     const float* bias;     // [4H] = b_ih + b_hh (folded into tab when TABLE)
     const float* tab;      // [V][4H]
     const int* token;      // [M]
+    int V;                 // rows of tab (tab_row)
     const int* flag;       // ENC: T_row[M];  PRED: emit[M]
     int t;                 // ENC: time step
     unsigned long long tile_mask;   // ENC: bit mt set iff m-tile mt has a row with t < T_row (host-computed:
@@ -592,7 +599,7 @@ struct EpiLSTM {
             if (!p.act) { p.h_old = Ops::ld(a.h_in, hidx(a, vr, u)); return p; }
         }
         if (TABLE) {
-            const float* tb = a.tab + (size_t)a.token[p.r] * 4 * H + u;
+            const float* tb = a.tab + tab_row(a.token[p.r], a.V) * 4 * H + u;
             p.x[0] = tb[0]; p.x[1] = tb[H]; p.x[2] = tb[2 * H]; p.x[3] = tb[3 * H];
         } else {
             p.x[0] = a.bias[u]; p.x[1] = a.bias[H + u]; p.x[2] = a.bias[2 * H + u]; p.x[3] = a.bias[3 * H + u];
@@ -677,6 +684,7 @@ struct NbrcArgs {
     const float* rbias;    // [3H] recurrent bias
     const float* tab;      // [V][3H]
     const int* token;
+    int V;                 // rows of tab (tab_row)
     const int* emit;
     const void* h_in;      // [M][H] current parity
     void* h_out;           // other parity
@@ -722,7 +730,7 @@ struct EpiNBRC {
         p.r = row_map[vr];
         p.h = Ops::ld(a.h_in, (size_t)(beam ? beam_prow(a.parent, a.W, p.r) : p.r) * H + u);
         if (TABLE) {
-            const float* tb = a.tab + (size_t)a.token[p.r] * 3 * H + u;
+            const float* tb = a.tab + tab_row(a.token[p.r], a.V) * 3 * H + u;
             p.xz = tb[0]; p.xr = tb[H]; p.xg = tb[2 * H];
         } else {
             p.xz = a.bias[u]; p.xr = a.bias[H + u]; p.xg = a.bias[2 * H + u];
@@ -791,7 +799,7 @@ struct EpiLSTMw {
             const int r = row_map[vr];
             float x[4];
             if (TABLE) {
-                const float* tb = a.tab + (size_t)a.token[r] * 4 * H + u;
+                const float* tb = a.tab + tab_row(a.token[r], a.V) * 4 * H + u;
                 x[0] = tb[0]; x[1] = tb[H]; x[2] = tb[2 * H]; x[3] = tb[3 * H];
             } else {
                 x[0] = a.bias[u]; x[1] = a.bias[H + u]; x[2] = a.bias[2 * H + u]; x[3] = a.bias[3 * H + u];
@@ -837,7 +845,7 @@ struct EpiNBRCw {
             const float h = Ops::ld(a.h_in, (size_t)(beam ? beam_prow(a.parent, a.W, r) : r) * H + u);
             float xz, xr, xg;
             if (TABLE) {
-                const float* tb = a.tab + (size_t)a.token[r] * 3 * H + u;
+                const float* tb = a.tab + tab_row(a.token[r], a.V) * 3 * H + u;
                 xz = tb[0]; xr = tb[H]; xg = tb[2 * H];
             } else {
                 xz = a.bias[u]; xr = a.bias[H + u]; xg = a.bias[2 * H + u];

@@ -372,12 +372,22 @@ __device__ __forceinline__ void wave_argmax_f64(double& best, int& ord) {
     best = b; ord = o;
 }
 
-// argmax of (float value, int index): larger value first, smaller index among equals
+// The order of every argmax that can become a token: numpy's and torch's.  NaN counts as the maximum (all NaN are equal), the
+// lowest index wins among equals, and a row in which nothing beats -inf (all -inf, or empty) gives index 0.  On values that are
+// not NaN amax_gt is `>` and amax_before the comparison it replaces, so finite rows decide exactly as before.
+__device__ __forceinline__ bool amax_gt(float x, float best) { return x > best || (x != x && best == best); }
+__device__ __forceinline__ bool amax_before(float x, int xi, float best, int bi) {
+    return amax_gt(x, best) || ((x == best || (x != x && best != best)) && xi < bi);
+}
+// the reduced index -> a token id: "no element won" (0x7fffffff) becomes 0; whatever comes out is in [0, V)
+__device__ __forceinline__ int amax_index(int arg, int V) { return (unsigned)arg < (unsigned)V ? arg : 0; }
+
+// argmax of (float value, int index) under amax_before: larger value first (NaN largest), smaller index among equals
 template <int CTRL>
 __device__ __forceinline__ void dpp_argmax32_step(float& best, int& arg) {
     const float ob = dpp_f32<CTRL>(best);
     const int oa = __builtin_amdgcn_update_dpp(0, arg, CTRL, 0xf, 0xf, false);
-    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+    if (amax_before(ob, oa, best, arg)) { best = ob; arg = oa; }
 }
 __device__ __forceinline__ void wave_argmax_f32(float& best, int& arg) {
     dpp_argmax32_step<0xB1>(best, arg); dpp_argmax32_step<0x4E>(best, arg); dpp_argmax32_step<0x141>(best, arg); dpp_argmax32_step<0x140>(best, arg);
@@ -387,7 +397,7 @@ __device__ __forceinline__ void wave_argmax_f32(float& best, int& arg) {
     for (int r = 16; r < 64; r += 16) {
         const float ob = readlane_f32(best, r);
         const int oa = __builtin_amdgcn_readlane(arg, r);
-        if (ob > b || (ob == b && oa < a)) { b = ob; a = oa; }
+        if (amax_before(ob, oa, b, a)) { b = ob; a = oa; }
     }
     best = b; arg = a;
 }
@@ -516,10 +526,10 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
         const float* z = logits + (size_t)(k * M + r) * V;
 #pragma unroll
         for (int q = 0; q < KEEP; ++q)
-            if (zv[k][q] > best[k]) { best[k] = zv[k][q]; arg[k] = tid + 256 * q; }
+            if (amax_gt(zv[k][q], best[k])) { best[k] = zv[k][q]; arg[k] = tid + 256 * q; }
         for (int j = tid + 256 * KEEP; j < V; j += 256) {
             const float x = z[j];
-            if (x > best[k]) { best[k] = x; arg[k] = j; }
+            if (amax_gt(x, best[k])) { best[k] = x; arg[k] = j; }
         }
         wave_argmax_f32(best[k], arg[k]);
         if (lane == 0) { sv[k][w] = best[k]; si[k][w] = arg[k]; }
@@ -531,7 +541,8 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
         best[k] = sv[k][0]; arg[k] = si[k][0];
 #pragma unroll
         for (int q = 1; q < 4; ++q)
-            if (sv[k][q] > best[k] || (sv[k][q] == best[k] && si[k][q] < arg[k])) { best[k] = sv[k][q]; arg[k] = si[k][q]; }
+            if (amax_before(sv[k][q], si[k][q], best[k], arg[k])) { best[k] = sv[k][q]; arg[k] = si[k][q]; }
+        arg[k] = amax_index(arg[k], V);
         const float* z = logits + (size_t)(k * M + r) * V;
         float sum = 0.f;
 #pragma unroll
@@ -614,13 +625,13 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
             if (j >= V) continue;
             const float jo = j == 0 ? s.lm_min : zl[q] / den;
             const float f = __fadd_rn(__fmul_rn(s.lm_alpha, lz[j]), __fmul_rn(s.lm_theta, jo));   // no FMA contraction
-            if (f > fb) { fb = f; fa = j; }
+            if (amax_gt(f, fb)) { fb = f; fa = j; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_xor(fb, o);
             const int oa = __shfl_xor(fa, o);
-            if (ob > fb || (ob == fb && oa < fa)) { fb = ob; fa = oa; }
+            if (amax_before(ob, oa, fb, fa)) { fb = ob; fa = oa; }
         }
         __syncthreads();
         if (lane == 0) { sv[0][w] = fb; si[0][w] = fa; }
@@ -628,8 +639,8 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
         fb = sv[0][0]; fa = si[0][0];
 #pragma unroll
         for (int q = 1; q < 4; ++q)
-            if (sv[0][q] > fb || (sv[0][q] == fb && si[0][q] < fa)) { fb = sv[0][q]; fa = si[0][q]; }
-        tok_e = fa;                          // the emitted token; log p stays the unfused one (models.py:422)
+            if (amax_before(sv[0][q], si[0][q], fb, fa)) { fb = sv[0][q]; fa = si[0][q]; }
+        tok_e = amax_index(fa, V);                          // the emitted token; log p stays the unfused one (models.py:422)
     }
     // ---- the decisions, in frame order (models.py:405-443, 530-571): a row consumes its run of blank frames and, if it
     // comes, the first token after it.  Every thread tracks t and the per-frame evaluation count; thread 0 owns the rest.
@@ -856,10 +867,10 @@ inline __global__ __launch_bounds__(256) void k_lm_quant(const float* __restrict
 inline __global__ __launch_bounds__(256) void k_lm_cell_q(const float* __restrict__ gx, const float* __restrict__ tab, const int* __restrict__ token,
                                                    const float* __restrict__ gh, const int* __restrict__ emit, float* __restrict__ h,
                                                    float* __restrict__ c, int H, int M, unsigned short* __restrict__ qh,
-                                                   float* __restrict__ sxh, int Kp) {
+                                                   float* __restrict__ sxh, int Kp, int V) {
     const int r = blockIdx.x, tid = threadIdx.x;
     if (!emit[r]) return;
-    const float* a = tab ? tab + (size_t)token[r] * 4 * H : gx + (size_t)r * 4 * H;
+    const float* a = tab ? tab + tab_row(token[r], V) * 4 * H : gx + (size_t)r * 4 * H;      // (tab_row: lasr_gemm.hip.h)
     const float* b = gh + (size_t)r * 4 * H;
     float hv[4];
     float mn = 0.f, mx = 0.f;
@@ -1042,10 +1053,10 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
 #pragma unroll
             for (int vw = 0; vw < VW; ++vw) {         // ascending v per lane: the first maximum wins
                 const int v = lane + 64 * vw + NTV * k;
-                if (v != s.blank && v < V && zl[vw][k] > x) { x = zl[vw][k]; a = v; }
+                if (v != s.blank && v < V && amax_gt(zl[vw][k], x)) { x = zl[vw][k]; a = v; }
             }
         wave_argmax_f32(x, a);
-        nb_arg = a;
+        nb_arg = amax_index(a, V);
     }
     if (dbg) s.dbg[2] = wall_clock64();
     if (!alb) {
@@ -1398,7 +1409,7 @@ __global__ __launch_bounds__(256) void k_beam_fuse(const float* __restrict__ log
             if (j >= V) continue;
             const float jo = j == 0 ? lm_min : zv[k] / den;
             const float f = __fadd_rn(__fmul_rn(alpha, lz[j]), __fmul_rn(theta, jo));   // no FMA contraction
-            if (f > fb) { fb = f; fa = j; }
+            if (amax_gt(f, fb)) { fb = f; fa = j; }
         }
         wave_argmax_f32(fb, fa);
         __syncthreads();
@@ -1407,7 +1418,8 @@ __global__ __launch_bounds__(256) void k_beam_fuse(const float* __restrict__ log
         fb = sv[0]; fa = si[0];
 #pragma unroll
         for (int k = 1; k < 4; ++k)
-            if (sv[k] > fb || (sv[k] == fb && si[k] < fa)) { fb = sv[k]; fa = si[k]; }
+            if (amax_before(sv[k], si[k], fb, fa)) { fb = sv[k]; fa = si[k]; }
+        fa = amax_index(fa, V);
         if (tid == 0) {
             s.token[r] = fa;
             s.trellis[(size_t)(s.cont ? iter_no % s.tring : iter_slot) * s.Md + r] = (par << 16) | (fa + 1);
@@ -1647,10 +1659,11 @@ inline __global__ __launch_bounds__(256) void k_logmel(const MelArgs a) {
     const int out_row = (!a.stream && a.by_value) ? (int)a.dst_row_v[row] : row;
     const long long base = (long long)t * a.hop - 512;
     auto sample = [&](int n) -> float {                  // windowed sample n of the 1024-frame
-        // the window is zero outside [win_off, win_off + win_len): decided from the index, so the
-        // window and the PCM loads are independent (no load -> branch -> load chain)
-        if (n < a.win_off || n >= a.win_off + a.win_len) return 0.f;
-        const float wv = a.window[n];
+        // The window is zero outside [win_off, win_off + win_len), and the sample is multiplied by that zero all the same, as
+        // torch.stft multiplies the whole n_fft frame by the zero-padded window: a finite sample gives +-0 (the power spectrum is
+        // the same bit for bit), a NaN or Inf sample makes every frame whose n_fft span holds it non-finite, as in the reference.
+        // The weight is decided from the index, so the window and the PCM loads are independent (no load -> branch -> load chain).
+        const float wv = (n < a.win_off || n >= a.win_off + a.win_len) ? 0.f : a.window[n];
         long long q = base + n;
         if (q < 0) q = -q;                               // reflect (torch.stft center=True, pad_mode="reflect")
         if (q >= N) q = 2 * (N - 1) - q;
@@ -1752,8 +1765,7 @@ __global__ __launch_bounds__(32 * NSTACK) void k_fe_mel(const FeMelArgs a) {
     const int N = a.n_window * a.chunk;
     const int base = (a.frame0 + f) * a.hop - 512;
     auto sample = [&](int n) -> float {
-        if (n < a.win_off || n >= a.win_off + a.win_len) return 0.f;
-        const float wv = a.window[n];
+        const float wv = (n < a.win_off || n >= a.win_off + a.win_len) ? 0.f : a.window[n];      // (zero weight: see k_logmel)
         int q = base + n;
         if (q < 0) q = -q;                               // reflect (torch.stft center=True, pad_mode="reflect")
         if (q >= N) q = 2 * (N - 1) - q;

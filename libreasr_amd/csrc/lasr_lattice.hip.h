@@ -89,7 +89,10 @@ struct LatDpArgs {
 };
 __device__ __forceinline__ double lat_logaddexp(double x, double z) {
     const double m = fmax(x, z);
-    if (m == -INFINITY) return m;                     // both predecessors impossible: no NaN from inf - inf
+    // both predecessors impossible: no NaN from inf - inf.  fmax drops a NaN operand, so (NaN, -inf) arrives here too (a NaN term
+    // on a cell with a single predecessor: frame 0, column 0): the sum is -inf for (-inf, -inf) and keeps that NaN, as
+    // np.logaddexp does
+    if (m == -INFINITY) return x + z;
     return m + log1p(exp(-fabs(x - z)));              // (one of them -inf: exp(-inf) = 0)
 }
 // Forward algorithm and Viterbi of one utterance per workgroup; threads run over u, anti-diagonals d = t + u in order.  Two

@@ -130,7 +130,7 @@ void launch_predictor_t(lasr_ctx* c, DecView& v, bool beam, int l0, int l1) {
         g.compact = c->ds.emit; g.M = c->Md; g.dbg = (c->dbg && v.dbg_gate) ? c->dbg + (size_t)(1 + std::min(l, 1)) * 4096 * 16 : nullptr;
         if (c->d.pred_cell == 1) {
             LstmArgs ea{};
-            ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.flag = c->ds.emit; ea.t = 0;
+            ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.V = c->d.vocab; ea.flag = c->ds.emit; ea.t = 0;
             ea.c = c->pred_c[wr][l]; ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l];
             ea.y = c->pred_y[wr][l]; ea.y_mt_total = 0; ea.y_mt_off = 0;
             ea.bn_s = L.bn_s; ea.bn_t = L.bn_t; ea.H = H; ea.M = c->Md; ea.MT = c->MTd;
@@ -140,7 +140,7 @@ void launch_predictor_t(lasr_ctx* c, DecView& v, bool beam, int l0, int l1) {
             else launch_lstm_cell<Ops, false>(c, v, wide8, wide, H, mgroups, g, ea);
         } else {
             NbrcArgs ea{};
-            ea.bias = L.bias; ea.rbias = L.rbias; ea.tab = L.tab; ea.token = c->ds.token; ea.emit = c->ds.emit;
+            ea.bias = L.bias; ea.rbias = L.rbias; ea.tab = L.tab; ea.token = c->ds.token; ea.V = c->d.vocab; ea.emit = c->ds.emit;
             ea.h_in = c->pred_h[p][l]; ea.h_out = c->pred_h[p ^ 1][l]; ea.y = c->pred_y[wr][l];
             ea.bn_s = L.bn_s; ea.bn_t = L.bn_t; ea.H = H; ea.M = c->Md;
             if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.y_in = c->pred_y[rd][l]; }
@@ -191,7 +191,7 @@ void launch_lm_t(lasr_ctx* c, DecView& v, bool beam, int l0, int l1, bool tail) 
         if (beam) { g.parent = c->b_parent; g.beam_w = c->W; }
         g.compact = c->ds.emit; g.M = R;
         LstmArgs ea{};
-        ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.flag = c->ds.emit; ea.t = 0;
+        ea.bias = L.bias; ea.tab = L.tab; ea.token = c->ds.token; ea.V = c->d.vocab; ea.flag = c->ds.emit; ea.t = 0;
         ea.c = m.cst[wr][l]; ea.h_in = m.h[p][l]; ea.h_out = m.h[p ^ 1][l]; ea.y = m.y[wr][l];
         ea.bn_s = m.ones; ea.bn_t = m.zeros; ea.H = H; ea.M = R; ea.MT = R / 16;
         if (beam) { ea.parent = c->b_parent; ea.W = c->W; ea.c_in = m.cst[rd][l]; ea.y_in = m.y[rd][l]; }

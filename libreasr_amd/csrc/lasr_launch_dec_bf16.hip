@@ -32,7 +32,7 @@ void launch_lm_q8(lasr_ctx* c, DecView& v) {
         lm_q_gemv_pre(c, v, m.qh[l], m.sxh[l], m.Kp_h, m.qWhh[l], m.s_hh[l], m.b_hh[l], m.gh, 4 * H, M);
         hipLaunchKernelGGL(k_lm_cell_q, dim3(M), dim3(256), 0, v.stream, (const float*)m.gx, (const float*)(l == 0 ? m.cells[0].tab : nullptr),
                            (const int*)c->ds.token, (const float*)m.gh, (const int*)c->ds.emit, (float*)m.h[0][l], m.cst[0][l], H, M,
-                           m.qh[l], m.sxh[l], m.Kp_h);
+                           m.qh[l], m.sxh[l], m.Kp_h, c->d.vocab);
     }
     v.lm_par ^= 1;
     lm_q_gemv_pre(c, v, m.qh[m.L - 1], m.sxh[m.L - 1], m.Kp_h, m.qWout, m.s_out, m.bout, m.raw, V, M);
