@@ -18,6 +18,7 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_cmd.hip.h"
 #include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
+#include "lasr_lattice_tables.hip.h"
 #include "lasr_lattice.hip.h"
 #include "lasr_lattice_post.hip.h"
 #include "lasr_prefix_tree.hip.h"
@@ -1647,88 +1648,129 @@ int lasr_step_wait(lasr_ctx* c, int* n_ran) {
 }
 
 // ---------------------------------------------------------------------------- offline
-int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples) {
-    RoctxRange roctx_range_("lasr_transcribe");
-    if (!c) return LASR_EINVAL;
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    RC(check_slots(c, slots, n, true));
-    if (n == 0) return LASR_OK;
-    if (!pcm || !n_samples) return fail(c, LASR_EINVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
+// The front half of every offline entry point (lasr_transcribe_*, lasr_align_*, lasr_score_*): frame counts from the lengths, then the
+// audio of the listed rows through the front-end and the encoder, behind a reset of the call's rows.
+struct OfflineDims {
+    std::vector<int> Tp, Tm;           // per utterance: encoder-input frames, log-mel frames (pcm only)
+    int T_max = 0, Tmel_max = 0;
+    long long total = 0;               // samples / frames of the call
+};
+// host arithmetic only: nothing has changed when they fail
+static int offline_dims_pcm(lasr_ctx* c, int n, const int64_t* n_samples, OfflineDims& D) {
     const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0; int Tmel_max = 0;
-    std::vector<int> Tp(n), Tm(n);
+    D.Tp.assign(n, 0); D.Tm.assign(n, 0);
     for (int i = 0; i < n; ++i) {
         if (n_samples[i] <= d.n_fft / 2) return fail(c, LASR_EINVAL, "utterance %d too short (%lld samples)", i, (long long)n_samples[i]);
-        Tm[i] = 1 + (int)(n_samples[i] / d.hop);
-        if (Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
-        Tp[i] = (Tm[i] - d.n_stack) / d.stride + 1;
-        T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
-        total += n_samples[i];
+        D.Tm[i] = 1 + (int)(n_samples[i] / d.hop);
+        if (D.Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
+        D.Tp[i] = (D.Tm[i] - d.n_stack) / d.stride + 1;
+        D.T_max = std::max(D.T_max, D.Tp[i]); D.Tmel_max = std::max(D.Tmel_max, D.Tm[i]);
+        D.total += n_samples[i];
     }
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
-    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
-    RC(cmd_begin(c));
-    long long off = 0;
+    return LASR_OK;
+}
+static int offline_dims_feats(lasr_ctx* c, int n, const int32_t* n_frames, OfflineDims& D) {
+    D.Tp.assign(n_frames, n_frames + n);
     for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        c->hc.T_row[s] = Tp[i]; c->hc.what[s] = 7; c->hc.row_frames[s] = Tm[i];
-        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
-        off += n_samples[i];
+        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
+        D.T_max = std::max(D.T_max, (int)n_frames[i]); D.total += n_frames[i];
+    }
+    return LASR_OK;
+}
+// Which rows a call touches.  audio [n]: the row that carries utterance i (lasr_score_*: its first candidate's; the other rows keep
+// T_row = 0).  reset [n_reset]: every row of the call, back to a fresh stream.  lattice: a lattice call marks its start for lat_times
+// in front of the reset; a decode call clears its beam records and marks behind it.
+struct OfflineRows { const int* audio; int n; const int* reset; int n_reset; bool lattice; };
+// inside the command the builder opened: the rows' reset, the commit, the reset itself and the call's first marker
+static int offline_reset(lasr_ctx* c, const OfflineRows& r) {
+    for (int j = 0; j < r.n_reset; ++j) {
+        const int s = r.reset[j];
+        c->hc.what[s] = 7;
         c->results[s].clear(); c->results[s].neg_logp = 0.0;
-        beam_host_reset(c, s, true);
+        if (!r.lattice) beam_host_reset(c, s, true);
     }
     RC(cmd_commit(c));
+    if (r.lattice) lat_mark(c, c->lat, 0);
     RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    rec(c, 0);
-    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
-    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    return decode_and_collect(c, T_max, d.max_iters_offline, true, std::vector<int>(slots, slots + n));
+    if (!r.lattice) rec(c, 0);
+    return LASR_OK;
+}
+// pcm [D.total] (host or device), the utterances concatenated: log-mel, stack + LayerNorm, encoder -> pe_sync
+static int offline_front_pcm(lasr_ctx* c, const float* pcm, const int64_t* n_samples, const OfflineDims& D, const OfflineRows& r) {
+    const lasr_model_desc& d = c->d;
+    RC(ensure_T(c, D.T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, pcm, (size_t)D.total, &c->stage_pcm, &c->stage_pcm_floats, &src));
+    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * D.Tmel_max * d.n_mels));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0; i < r.n; ++i) {
+        const int s = r.audio[i];
+        c->hc.T_row[s] = D.Tp[i]; c->hc.row_frames[s] = D.Tm[i];
+        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
+        off += n_samples[i];
+    }
+    RC(offline_reset(c, r));
+    launch_logmel_offline(c, src, 0, c->M, D.Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
+    stack_ln_logmel(c, c->lm_buf, D.Tmel_max, d.stride, c->dc.T_row, D.T_max);
+    RC(commit_T_rows(c, D.T_max));
+    encode_step(c, D.T_max);
+    return LASR_OK;
+}
+// feats [D.total][feat] (host or device): stack + LayerNorm, encoder -> pe_sync
+static int offline_front_feats(lasr_ctx* c, const float* feats, const OfflineDims& D, const OfflineRows& r) {
+    RC(ensure_T(c, D.T_max));
+    const float* src = nullptr;
+    RC(stage_to_device(c, feats, (size_t)D.total * c->d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
+    RC(cmd_begin(c));
+    long long off = 0;
+    for (int i = 0; i < r.n; ++i) {
+        c->hc.T_row[r.audio[i]] = D.Tp[i]; c->hc.row_feat_off[r.audio[i]] = off;
+        off += D.Tp[i];
+    }
+    RC(offline_reset(c, r));
+    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, D.T_max);
+    RC(commit_T_rows(c, D.T_max));
+    encode_step(c, D.T_max);
+    return LASR_OK;
 }
 
-int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames) {
+// either kind of audio of a call: pcm with n_samples or stacked features with n_frames (the other null), utterances concatenated
+struct OfflineAudio {
+    const float* data; const int64_t* n_samples; const int32_t* n_frames;
+    bool given() const { return data && (n_samples || n_frames); }
+};
+static int offline_dims(lasr_ctx* c, int n, const OfflineAudio& au, OfflineDims& D) {
+    return au.n_samples ? offline_dims_pcm(c, n, au.n_samples, D) : offline_dims_feats(c, n, au.n_frames, D);
+}
+static int offline_front(lasr_ctx* c, const OfflineAudio& au, const OfflineDims& D, const OfflineRows& r) {
+    return au.n_samples ? offline_front_pcm(c, au.data, au.n_samples, D, r) : offline_front_feats(c, au.data, D, r);
+}
+
+static int transcribe_impl(lasr_ctx* c, const int* slots, int n, const OfflineAudio& au) {
     if (!c) return LASR_EINVAL;
     RC(flush_lazy(c));
     RC(require_idle(c));
     RC(check_slots(c, slots, n, true));
     if (n == 0) return LASR_OK;
-    if (!feats || !n_frames) return fail(c, LASR_EINVAL, "null argument");
+    if (!au.given()) return fail(c, LASR_EINVAL, "null argument");
     HIPCHK(c, hipSetDevice(c->device));
-    const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
-        T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
-    }
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
-    RC(cmd_begin(c));
-    long long off = 0;
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        c->hc.T_row[s] = n_frames[i]; c->hc.what[s] = 7; c->hc.row_feat_off[s] = off;
-        off += n_frames[i];
-        c->results[s].clear(); c->results[s].neg_logp = 0.0;
-        beam_host_reset(c, s, true);
-    }
-    RC(cmd_commit(c));
-    RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    rec(c, 0);
-    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    return decode_and_collect(c, T_max, d.max_iters_offline, true, std::vector<int>(slots, slots + n));
+    OfflineDims D;
+    RC(offline_dims(c, n, au, D));
+    RC(offline_front(c, au, D, OfflineRows{slots, n, slots, n, false}));
+    return decode_and_collect(c, D.T_max, c->d.max_iters_offline, true, std::vector<int>(slots, slots + n));
+}
+int lasr_transcribe_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples) {
+    RoctxRange roctx_range_("lasr_transcribe");
+    return transcribe_impl(c, slots, n, OfflineAudio{pcm, n_samples, nullptr});
+}
+int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames) {
+    return transcribe_impl(c, slots, n, OfflineAudio{feats, nullptr, n_frames});
 }
 
-// ---------------------------------------------------------------------------- teacher-forced lattice (DESIGN 5.3)
+// ---------------------------------------------------------------------------- teacher-forced lattice (DESIGN 5.3, 5.5, 5.6)
 // The banded lattice is compiled at the END of this unit -- lasr_lattice_band.hip.h and its entry points follow the
-// last function below, so nothing that was here before moves -- and lasr_align_*'s two bodies reach it through these declarations.
+// last function below -- and align_impl reaches it through these declarations.
 namespace lasr {
 constexpr int LAT_BAND_WMAX = 1536;    // window width: four diagonals of doubles (48 KB) + 16 KB of back-pointers = 64 KB of LDS
 constexpr int LAT_BAND_UMAX = 32767;   // labels per transcript of a banded call (the teacher-forced predictor keeps (U + 1) rows x J)
@@ -1738,17 +1780,6 @@ struct LatBandIO;
 int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io);
 int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io);
 }
-// common head of lasr_align_*: a greedy, idle context, open slots, a valid transcript per utterance -- nothing has changed when it fails
-static int align_prologue(lasr_ctx* c, const int* slots, int n, const void* audio, const void* lens, const int32_t* tokens,
-                          const int32_t* n_tokens, const double* loglik, int umax = LAT_UMAX) {
-    if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_align_*: greedy contexts only (beam = %d)", c->W);
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    RC(check_slots(c, slots, n, true));
-    if (n == 0) return LASR_OK;
-    if (!audio || !lens || !loglik) return fail(c, LASR_EINVAL, "null argument");
-    return lat_check_tokens(c, n, tokens, n_tokens, umax);
-}
 // a posterior call keeps alpha and beta of every cell: refused beyond LAT_POST_CELLS, before anything is read or changed
 static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) {
     long long cells = 0;
@@ -1756,158 +1787,110 @@ static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) 
     if (cells > LAT_POST_CELLS) return fail(c, LASR_EINVAL, "posteriors of a lattice of %lld cells (at most %lld)", cells, LAT_POST_CELLS);
     return LASR_OK;
 }
-// lasr_align_pcm; post: the posterior outputs of lasr_align_post_pcm (null: none); band: lasr_align_band_pcm (null: the full lattice)
-static int align_pcm_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
-                          const int32_t* n_tokens, const LatOut& o, const LatPostOut* post, const LatBandIO* band = nullptr) {
+// lasr_align_*.  post: the posterior outputs of lasr_align_post_* (null: none); band: lasr_align_band_* (null: the full lattice).
+// A greedy, idle context, open slots, a valid transcript per utterance, and the refusals that need the frame counts: nothing has
+// changed when it fails before the front half
+struct AlignCall { const int* slots; int n; const int32_t* tokens; const int32_t* n_tokens; LatOut o; const LatPostOut* post; const LatBandIO* band; };
+static int align_impl(lasr_ctx* c, const AlignCall& a, const OfflineAudio& au) {
     if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, pcm, n_samples, tokens, n_tokens, o.loglik, band ? LAT_BAND_UMAX : LAT_UMAX));
-    if (n == 0) return LASR_OK;
+    if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_align_*: greedy contexts only (beam = %d)", c->W);
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    RC(check_slots(c, a.slots, a.n, true));
+    if (a.n == 0) return LASR_OK;
+    if (!au.given() || !a.o.loglik) return fail(c, LASR_EINVAL, "null argument");
+    RC(lat_check_tokens(c, a.n, a.tokens, a.n_tokens, a.band ? LAT_BAND_UMAX : LAT_UMAX));
     HIPCHK(c, hipSetDevice(c->device));
-    const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0; int Tmel_max = 0;
-    std::vector<int> Tp(n), Tm(n);
-    for (int i = 0; i < n; ++i) {
-        if (n_samples[i] <= d.n_fft / 2) return fail(c, LASR_EINVAL, "utterance %d too short (%lld samples)", i, (long long)n_samples[i]);
-        Tm[i] = 1 + (int)(n_samples[i] / d.hop);
-        if (Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
-        Tp[i] = (Tm[i] - d.n_stack) / d.stride + 1;
-        T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
-        total += n_samples[i];
-    }
-    if (post) RC(post_check_cells(c, Tp.data(), n_tokens, n));
-    if (band) RC(lat_band_plan(c, Tp.data(), n_tokens, n, *band));
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
-    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
-    RC(cmd_begin(c));
-    long long off = 0;
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        c->hc.T_row[s] = Tp[i]; c->hc.what[s] = 7; c->hc.row_frames[s] = Tm[i];
-        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
-        off += n_samples[i];
-        c->results[s].clear(); c->results[s].neg_logp = 0.0;
-    }
-    RC(cmd_commit(c));
-    lat_mark(c, c->lat, 0);
-    RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
-    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    if (band) return lat_finish_band(c, slots, n, tokens, o, *band);
-    return lat_finish(c, slots, n, Tp.data(), tokens, n_tokens, o, post);
-}
-static int align_feats_impl(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
-                            const int32_t* n_tokens, const LatOut& o, const LatPostOut* post, const LatBandIO* band = nullptr) {
-    if (!c) return LASR_EINVAL;
-    RC(align_prologue(c, slots, n, feats, n_frames, tokens, n_tokens, o.loglik, band ? LAT_BAND_UMAX : LAT_UMAX));
-    if (n == 0) return LASR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
-        T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
-    }
-    if (post) RC(post_check_cells(c, n_frames, n_tokens, n));
-    if (band) RC(lat_band_plan(c, n_frames, n_tokens, n, *band));
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
-    RC(cmd_begin(c));
-    long long off = 0;
-    for (int i = 0; i < n; ++i) {
-        const int s = slots[i];
-        c->hc.T_row[s] = n_frames[i]; c->hc.what[s] = 7; c->hc.row_feat_off[s] = off;
-        off += n_frames[i];
-        c->results[s].clear(); c->results[s].neg_logp = 0.0;
-    }
-    RC(cmd_commit(c));
-    lat_mark(c, c->lat, 0);
-    RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    if (band) return lat_finish_band(c, slots, n, tokens, o, *band);
-    return lat_finish(c, slots, n, n_frames, tokens, n_tokens, o, post);
+    OfflineDims D;
+    RC(offline_dims(c, a.n, au, D));
+    if (a.post) RC(post_check_cells(c, D.Tp.data(), a.n_tokens, a.n));
+    if (a.band) RC(lat_band_plan(c, D.Tp.data(), a.n_tokens, a.n, *a.band));
+    RC(offline_front(c, au, D, OfflineRows{a.slots, a.n, a.slots, a.n, true}));
+    if (a.band) return lat_finish_band(c, a.slots, a.n, a.tokens, a.o, *a.band);
+    return lat_finish(c, a.slots, a.n, D.Tp.data(), a.tokens, a.n_tokens, a.o, a.post);
 }
 int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
                    const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
-    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, nullptr};
+    return align_impl(c, a, OfflineAudio{pcm, n_samples, nullptr});
 }
 int lasr_align_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
                      const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp) {
-    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, nullptr};
+    return align_impl(c, a, OfflineAudio{feats, nullptr, n_frames});
 }
 // lasr_align_* with the lattice's edge posteriors; all six posterior outputs null: lasr_align_* itself
 int lasr_align_post_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
                         const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp,
                         float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
     const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
-    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp},
-                          lat_post_any(p) ? &p : nullptr);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, lat_post_any(p) ? &p : nullptr, nullptr};
+    return align_impl(c, a, OfflineAudio{pcm, n_samples, nullptr});
 }
 int lasr_align_post_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
                           const int32_t* n_tokens, double* loglik, double* viterbi, int32_t* frames, float* logps, float* blank_lp, float* emit_lp,
                           float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
     const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
-    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp},
-                            lat_post_any(p) ? &p : nullptr);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, lat_post_any(p) ? &p : nullptr, nullptr};
+    return align_impl(c, a, OfflineAudio{feats, nullptr, n_frames});
 }
-// the dynamic programme alone, on the caller's lattices (host or device); T, U and the results are host memory; blocking
-int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
-                    double* viterbi, int32_t* frames) {
-    if (!c) return LASR_EINVAL;
+// ---- the dynamic programmes alone, on the caller's lattices (host or device); sizes and results are host memory; blocking
+// behind the call's tables: the two lattices to the device (a device pointer is used where it is), what `run` enqueues over them, and
+// the stream drained
+extern "C++" template <class Run>
+static int lattice_hook(lasr_ctx* c, const float* blank_lp, const float* emit_lp, long long cells, Run run) {
+    lasr_ctx::Lattice& w = c->lat;
+    const float *b = nullptr, *e = nullptr;
+    RC(stage_to_device(c, blank_lp, (size_t)cells, &w.b, &w.b_n, &b));
+    RC(stage_to_device(c, emit_lp, (size_t)cells, &w.e, &w.e_n, &e));
+    RC(run(b, e));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return LASR_OK;
+}
+// head of lasr_lattice_dp / lasr_lattice_post: the arguments, and the call description with every utterance on row 0
+static int lattice_call(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, const double* loglik,
+                        LatCall& k) {
     if (!blank_lp || !emit_lp || !T || !U || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
-    LatCall k;
     k.n = n;
     k.T.assign(T, T + n); k.U.assign(U, U + n); k.slot.assign(n, 0);
     for (int i = 0; i < n; ++i)
         if (T[i] < 1 || U[i] < 0 || U[i] > LAT_UMAX) return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d (T >= 1, 0 <= U <= %d)", i, T[i], U[i], LAT_UMAX);
-    HIPCHK(c, hipSetDevice(c->device));
-    lasr_ctx::Lattice& w = c->lat;
-    std::vector<long long> img;
-    RC(lat_upload(c, w, k, nullptr, img));
-    const float *b = nullptr, *e = nullptr;
-    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
-    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
-    const bool vit = viterbi || frames;
-    RC(lat_run_dp(c, w, k, b, e, vit, frames != nullptr, false));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
     return LASR_OK;
 }
-// the forward-backward programme alone, on the caller's lattices (host or device, as lasr_lattice_dp); results are host memory; blocking
+// layout and tables of a full-lattice hook's call -> device (no labels: the programmes read none)
+static int lattice_tables(lasr_ctx* c, LatCall& k, TabImage& img) {
+    HIPCHK(c, hipSetDevice(c->device));
+    RC(lat_layout_checked(c, k));
+    lat_pack(k, nullptr, img);
+    return lat_upload(c, c->lat, img);
+}
+int lasr_lattice_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
+                    double* viterbi, int32_t* frames) {
+    if (!c) return LASR_EINVAL;
+    LatCall k;
+    TabImage img;
+    RC(lattice_call(c, blank_lp, emit_lp, T, U, n, loglik, k));
+    RC(lattice_tables(c, k, img));
+    RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) {
+        return lat_run_dp(c, c->lat, k, b, e, viterbi || frames, frames != nullptr, false);
+    }));
+    return lat_copy_out(c, c->lat, k, LatOut{loglik, viterbi, frames, nullptr, nullptr, nullptr});
+}
+// the forward-backward programme
 int lasr_lattice_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n, double* loglik,
                       double* loglik_bwd, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame,
                       double* tok_peak) {
     if (!c) return LASR_EINVAL;
-    if (!blank_lp || !emit_lp || !T || !U || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
     LatCall k;
-    k.n = n;
-    k.T.assign(T, T + n); k.U.assign(U, U + n); k.slot.assign(n, 0);
-    for (int i = 0; i < n; ++i)
-        if (T[i] < 1 || U[i] < 0 || U[i] > LAT_UMAX) return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d (T >= 1, 0 <= U <= %d)", i, T[i], U[i], LAT_UMAX);
+    TabImage img;
+    RC(lattice_call(c, blank_lp, emit_lp, T, U, n, loglik, k));
     RC(post_check_cells(c, T, U, n));
-    HIPCHK(c, hipSetDevice(c->device));
-    lasr_ctx::Lattice& w = c->lat;
-    std::vector<long long> img;
-    RC(lat_upload(c, w, k, nullptr, img));
-    const float *b = nullptr, *e = nullptr;
-    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
-    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
+    RC(lattice_tables(c, k, img));
     const LatPostOut p{loglik, loglik_bwd, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
-    RC(lat_post_launch(c, w, k, b, e, p));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return lat_post_copy(c, w, k, p);
+    RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) { return lat_post_launch(c, c->lat, k, b, e, p); }));
+    return lat_post_copy(c, c->lat, k, p);
 }
-
 // ---------------------------------------------------------------------------- n-best rescoring over a prefix tree
 int lasr_prefix_tree(const int32_t* tokens, const int32_t* n_tokens, int k, int cap, int32_t* parent, int32_t* label, int32_t* depth,
                      int32_t* term, int* n_nodes) {
@@ -1944,84 +1927,28 @@ static int score_prologue(lasr_ctx* c, const int* slots, int n, const void* audi
     *K = k;
     return LASR_OK;
 }
-int lasr_score_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* n_cands,
-                   const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp) {
+static int score_impl(lasr_ctx* c, const int* slots, int n, const OfflineAudio& au, const int32_t* n_cands, const int32_t* tokens,
+                      const int32_t* n_tokens, const TreeOut& o) {
     if (!c) return LASR_EINVAL;
     int K = 0;
     std::vector<lasr_pt::Tree> trees;
-    RC(score_prologue(c, slots, n, pcm, n_samples, n_cands, tokens, n_tokens, loglik, &K, trees));
+    RC(score_prologue(c, slots, n, au.data, au.n_samples ? (const void*)au.n_samples : au.n_frames, n_cands, tokens, n_tokens, o.loglik, &K, trees));
     if (n == 0) return LASR_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0; int Tmel_max = 0;
-    std::vector<int> Tp(n), Tm(n);
-    for (int i = 0; i < n; ++i) {
-        if (n_samples[i] <= d.n_fft / 2) return fail(c, LASR_EINVAL, "utterance %d too short (%lld samples)", i, (long long)n_samples[i]);
-        Tm[i] = 1 + (int)(n_samples[i] / d.hop);
-        if (Tm[i] < d.n_stack) return fail(c, LASR_EINVAL, "utterance %d yields no stacked frame", i);
-        Tp[i] = (Tm[i] - d.n_stack) / d.stride + 1;
-        T_max = std::max(T_max, Tp[i]); Tmel_max = std::max(Tmel_max, Tm[i]);
-        total += n_samples[i];
-    }
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, pcm, (size_t)total, &c->stage_pcm, &c->stage_pcm_floats, &src));
-    RC(ensure_buf(c, &c->lm_buf, &c->lm_floats, (size_t)c->M * Tmel_max * d.n_mels));
-    RC(cmd_begin(c));
-    long long off = 0;
-    for (int i = 0, j = 0; i < n; ++i) {
-        const int s = slots[j];                       // the audio lives on the row of the first candidate; the others keep T_row = 0
-        c->hc.T_row[s] = Tp[i]; c->hc.row_frames[s] = Tm[i];
-        c->hc.row_N[s] = n_samples[i]; c->hc.row_src_off[s] = off;
-        off += n_samples[i];
-        for (int q = 0; q < n_cands[i]; ++q, ++j) {
-            c->hc.what[slots[j]] = 7;
-            c->results[slots[j]].clear(); c->results[slots[j]].neg_logp = 0.0;
-        }
-    }
-    RC(cmd_commit(c));
-    lat_mark(c, c->lat, 0);
-    RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    launch_logmel_offline(c, src, 0, c->M, Tmel_max, c->lm_buf, c->dc.row_N, c->dc.row_src_off, c->dc.row_frames);
-    stack_ln_logmel(c, c->lm_buf, Tmel_max, d.stride, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    return tree_finish(c, slots, n, n_cands, Tp.data(), tokens, n_tokens, trees, TreeOut{loglik, viterbi, blank_lp, emit_lp});
+    OfflineDims D;
+    RC(offline_dims(c, n, au, D));
+    std::vector<int> first(n);                        // the audio of an utterance lives on the row of its first candidate
+    for (int i = 0, j = 0; i < n; j += n_cands[i], ++i) first[i] = slots[j];
+    RC(offline_front(c, au, D, OfflineRows{first.data(), n, slots, K, true}));
+    return tree_finish(c, slots, n, n_cands, D.Tp.data(), tokens, n_tokens, trees, o);
+}
+int lasr_score_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* n_cands,
+                   const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp) {
+    return score_impl(c, slots, n, OfflineAudio{pcm, n_samples, nullptr}, n_cands, tokens, n_tokens, TreeOut{loglik, viterbi, blank_lp, emit_lp});
 }
 int lasr_score_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* n_cands,
                      const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp) {
-    if (!c) return LASR_EINVAL;
-    int K = 0;
-    std::vector<lasr_pt::Tree> trees;
-    RC(score_prologue(c, slots, n, feats, n_frames, n_cands, tokens, n_tokens, loglik, &K, trees));
-    if (n == 0) return LASR_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const lasr_model_desc& d = c->d;
-    long long total = 0; int T_max = 0;
-    for (int i = 0; i < n; ++i) {
-        if (n_frames[i] < 1) return fail(c, LASR_EINVAL, "utterance %d has no frames", i);
-        T_max = std::max(T_max, (int)n_frames[i]); total += n_frames[i];
-    }
-    RC(ensure_T(c, T_max));
-    const float* src = nullptr;
-    RC(stage_to_device(c, feats, (size_t)total * d.feat, &c->feat_stage, &c->feat_stage_floats, &src));
-    RC(cmd_begin(c));
-    long long off = 0;
-    for (int i = 0, j = 0; i < n; ++i) {
-        c->hc.T_row[slots[j]] = n_frames[i]; c->hc.row_feat_off[slots[j]] = off;      // (the first candidate's row; the others: T_row = 0)
-        off += n_frames[i];
-        for (int q = 0; q < n_cands[i]; ++q, ++j) {
-            c->hc.what[slots[j]] = 7;
-            c->results[slots[j]].clear(); c->results[slots[j]].neg_logp = 0.0;
-        }
-    }
-    RC(cmd_commit(c));
-    lat_mark(c, c->lat, 0);
-    RC(apply_reset(c, sync_view(c, c->la_offline), true));
-    stack_ln_feats(c, src, c->dc.row_feat_off, c->dc.T_row, T_max);
-    RC(commit_T_rows(c, T_max));
-    encode_step(c, T_max);
-    return tree_finish(c, slots, n, n_cands, n_frames, tokens, n_tokens, trees, TreeOut{loglik, viterbi, blank_lp, emit_lp});
+    return score_impl(c, slots, n, OfflineAudio{feats, nullptr, n_frames}, n_cands, tokens, n_tokens, TreeOut{loglik, viterbi, blank_lp, emit_lp});
 }
 // the tree dynamic programme alone, on the caller's lattices (host or device); T, n_nodes, parent and the results are host memory; blocking
 // (contiguous children are NOT required here: only k_lat_dp_tree runs, which reads parent / depth / dstart; the child tables that
@@ -2050,14 +1977,9 @@ int lasr_lattice_tree_dp(lasr_ctx* c, const float* blank_lp, const float* emit_l
     }
     HIPCHK(c, hipSetDevice(c->device));
     lasr_ctx::Lattice& w = c->lat;
-    std::vector<long long> img;
+    TabImage img;
     RC(tree_upload(c, w, k, img));
-    const float *b = nullptr, *e = nullptr;
-    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
-    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
-    RC(tree_run_dp(c, w, k, b, e, viterbi != nullptr));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
+    RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) { return tree_run_dp(c, w, k, b, e, viterbi != nullptr); }));
     HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
     if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + k.nodes, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
     return LASR_OK;
@@ -3112,52 +3034,51 @@ int lasr_bench_cell(lasr_ctx* c, int layer, int iters, double* us) {
 // ---------------------------------------------------------------------------- banded lattice
 #include "lasr_band_windows.hip.h"
 #include "lasr_lattice_band.hip.h"
+extern "C" {
+// lasr_align_* over a band of `band` labels per frame
 int lasr_band_windows(int T, int U, int band, const int32_t* frames, const int32_t* lo_cur, int32_t* lo_out, int* touch) {
     return lasr_bw::band_windows(T, U, band, frames, lo_cur, lo_out, touch);
 }
 int lasr_align_band_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
                         const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
                         int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch) {
-    LatBandCall k;
+    LatCall k;
     const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
-    return align_pcm_impl(c, slots, n, pcm, n_samples, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io};
+    return align_impl(c, a, OfflineAudio{pcm, n_samples, nullptr});
 }
 int lasr_align_band_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
                           const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
                           int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch) {
-    LatBandCall k;
+    LatCall k;
     const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
-    return align_feats_impl(c, slots, n, feats, n_frames, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io);
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io};
+    return align_impl(c, a, OfflineAudio{feats, nullptr, n_frames});
 }
-// the banded dynamic programme alone, on the caller's band lattices (host or device); T, U, W, lo and the results are host memory; blocking
+
+// the banded programme: W and lo [sum T] beside T and U
 int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
                          const int32_t* lo, int n, double* loglik, double* viterbi, int32_t* frames) {
     if (!c) return LASR_EINVAL;
     if (!blank_lp || !emit_lp || !T || !U || !W || !lo || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
-    LatBandCall k;
+    LatCall k;
+    TabImage img;
     k.n = n;
     k.T.assign(T, T + n); k.U.assign(U, U + n); k.W.assign(W, W + n); k.slot.assign(n, 0);
     for (int i = 0; i < n; ++i)
         if (T[i] < 1 || U[i] < 0 || U[i] > LAT_BAND_UMAX || W[i] < 1 || W[i] > std::min(U[i] + 1, LAT_BAND_WMAX) || (T[i] == 1 && W[i] != U[i] + 1))
             return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d, W = %d (T >= 1, 0 <= U <= %d, 1 <= W <= min(U + 1, %d), W = U + 1 where T = 1)",
                         i, T[i], U[i], W[i], LAT_BAND_UMAX, LAT_BAND_WMAX);
-    RC(lat_band_layout(c, k));
+    RC(lat_layout_checked(c, k));
     k.lo.assign(lo, lo + k.sumT);
     for (int i = 0; i < n; ++i)
         if (!lasr_bw::valid(T[i], U[i], W[i], lo + k.lo_off[i])) return fail(c, LASR_EINVAL, "lattice %d: lo is not a valid set of windows of width %d", i, W[i]);
     HIPCHK(c, hipSetDevice(c->device));
-    lasr_ctx::Lattice& w = c->lat;
-    std::vector<long long> img;
-    RC(lat_band_upload(c, w, k, nullptr, img));
-    const float *b = nullptr, *e = nullptr;
-    RC(stage_to_device(c, blank_lp, (size_t)k.cells, &w.b, &w.b_n, &b));
-    RC(stage_to_device(c, emit_lp, (size_t)k.cells, &w.e, &w.e_n, &e));
-    const bool vit = viterbi || frames;
-    RC(lat_band_run_dp(c, w, k, b, e, vit, frames != nullptr, false));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (frames && k.sumU) HIPCHK(c, hipMemcpy(frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
-    return LASR_OK;
+    lat_pack(k, nullptr, img);
+    RC(lat_upload(c, c->lat, img));
+    RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) {
+        return lat_band_run_dp(c, c->lat, k, b, e, viterbi || frames, frames != nullptr, false);
+    }));
+    return lat_copy_out(c, c->lat, k, LatOut{loglik, viterbi, frames, nullptr, nullptr, nullptr});
 }
+}  // extern "C"

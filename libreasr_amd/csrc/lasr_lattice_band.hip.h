@@ -2,62 +2,17 @@
 // lasr_align_band_feats / lasr_lattice_band_dp): frame t owns the columns [lo[t], lo[t] + w) (lasr_band_windows.hip.h), the
 // joint is evaluated on those cells alone and both recursions of lasr_lattice.hip.h run on them, a predecessor outside its frame's
 // window counting -inf.  Cost and workspace grow with T w instead of T (U + 1), and the dynamic programme's LDS with w alone.
-// Engine unit only (lasr_engine.hip), included at its end, after lasr_band_windows.hip.h: the unit's earlier kernels and functions stay
-// where they were; LAT_BAND_WMAX / LAT_BAND_UMAX and the two functions lasr_align_*'s bodies call are declared in front of those.
+// Engine unit only (lasr_engine.hip), included at its end, after lasr_band_windows.hip.h (DESIGN 5.6 has the measurement behind that
+// place); LAT_BAND_WMAX / LAT_BAND_UMAX and the two functions align_impl calls are declared in the unit, in front of align_impl.
 //
 // Band layout: cell = off_i + t w_i + k with u = lo[t] + k -- the flat order of the blocks and of the two lattice arrays.
-//   k_lat_ja_band / k_lat_pick_band   k_lat_ja / k_lat_pick with a row mapped to (t, lo[t] + k); the same LAT_R blocks, logits GEMM and
-//                                     reduction order, so a term has the bits lasr_align_* gives the same cell
-//   k_lat_dp_band                     both recursions of one utterance per workgroup over anti-diagonals, LDS indexed by t mod w
+//   LatBandMap      (lasr_lattice.hip.h) that layout for k_lat_ja / k_lat_pick: the same LAT_R blocks, logits GEMM, lat_row_lse and
+//                   label tail, so from the same logits a term has the bits lasr_align_* gives the same cell
+//   k_lat_dp_band   both recursions of one utterance per workgroup over anti-diagonals, LDS indexed by t mod w
+// The call description, its layout and its tables are lasr_lattice_tables.hip.h's LatCall with W and lo set.
 #pragma once
 
 namespace lasr {
-
-struct LatBandTab {
-    LatTab tb;                         // off: first BAND cell of the utterance
-    const int* W;                      // [n] window width
-    const int* lo_off;                 // [n] first frame in lo
-    const int* lo;                     // [sum T] window starts
-};
-
-inline __global__ __launch_bounds__(256) void k_lat_ja_band(const float* __restrict__ pe, const float* __restrict__ lat_pp, const LatBandTab bt,
-                                                            long long cell0, int n_rows, void* __restrict__ ja, int J, int M, int Ml, int mt, int bf) {
-    const int row = blockIdx.x;
-    if (row >= n_rows) return;
-    const long long cell = cell0 + row;
-    const int i = lat_find(bt.tb, cell);
-    const int w = bt.W[i], rel = (int)(cell - bt.tb.off[i]);
-    const int t = rel / w, u = bt.lo[bt.lo_off[i] + t] + (rel - t * w), s = bt.tb.slot[i];
-    const float* e = pe + ((size_t)t * M + s) * J;
-    const float* p = lat_pp + ((size_t)u * Ml + s) * J;
-    for (int j = threadIdx.x; j < J; j += 256) act_st(bf, ja, act_off(bf, row, j, mt), tanhf(e[j] + p[j]));
-}
-
-// k_lat_pick's maximum, exp-sum and their order (k_select's), one wave per row
-inline __global__ __launch_bounds__(256) void k_lat_pick_band(const float* __restrict__ logits, const LatBandTab bt, long long cell0, int n_rows,
-                                                              int V, int blank, float* __restrict__ b_out, float* __restrict__ e_out) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n_rows) return;                       // wave-uniform
-    const float* z = logits + (size_t)row * V;
-    float m = -INFINITY;
-    for (int j = lane; j < V; j += 64) m = fmaxf(m, z[j]);
-    m = wave_max_f32(m);
-    float sum = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        float part = 0.f;
-        for (int j = lane + 64 * w; j < V; j += 256) part += expf(z[j] - m);
-        sum += wave_sum_f32(part);
-    }
-    if (lane != 0) return;
-    const float lse = logf(sum);
-    const long long cell = cell0 + row;
-    const int i = lat_find(bt.tb, cell);
-    const int Ui = bt.tb.U[i], wi = bt.W[i], rel = (int)(cell - bt.tb.off[i]);
-    const int t = rel / wi, u = bt.lo[bt.lo_off[i] + t] + (rel - t * wi);
-    b_out[cell] = (z[blank] - m) - lse;
-    e_out[cell] = u < Ui ? (z[bt.tb.tok[bt.tb.tok_off[i] + u]] - m) - lse : 0.f;
-}
 
 struct LatBandDpArgs {
     const float* b; const float* e;   // [cells] each, band layout
@@ -170,73 +125,16 @@ __global__ __launch_bounds__(256) void k_lat_dp_band(const LatBandDpArgs a) {
 
 namespace {
 
-// host image of a banded call's tables and their device views
-struct LatBandCall {
-    int n = 0;
-    std::vector<int> T, U, W, slot, tok_off, lo_off;
-    std::vector<int32_t> lo;                          // [sum T] the windows of the pass
-    std::vector<long long> off, bp_off;
-    long long cells = 0, sumU = 0, sumT = 0, bp_words = 0;
-    int Umax = 0, Wmax = 0, lds_bp_words = 0;
-    LatBandTab tab{};
-    const long long* d_bp_off = nullptr;
-};
-// offsets and sizes from T / U / W (host only); LASR_EINVAL beyond 2^31 - 1 cells
-int lat_band_layout(lasr_ctx* c, LatBandCall& k) {
-    const int n = k.n;
-    k.off.assign(n + 1, 0); k.tok_off.assign(n, 0); k.lo_off.assign(n, 0); k.bp_off.assign(n, 0);
-    k.cells = k.sumU = k.sumT = k.bp_words = 0; k.Umax = k.Wmax = k.lds_bp_words = 0;
-    for (int i = 0; i < n; ++i) {
-        k.off[i] = k.cells; k.tok_off[i] = (int)k.sumU; k.lo_off[i] = (int)k.sumT;
-        const long long ci = (long long)k.T[i] * k.W[i], wi = (ci + 31) >> 5;
-        k.bp_off[i] = k.bp_words;
-        if (wi > LAT_BP_WORDS) k.bp_words += wi; else k.lds_bp_words = std::max(k.lds_bp_words, (int)wi);
-        k.cells += ci; k.sumU += k.U[i]; k.sumT += k.T[i];
-        k.Umax = std::max(k.Umax, k.U[i]); k.Wmax = std::max(k.Wmax, k.W[i]);
-    }
-    k.off[n] = k.cells;
-    if (k.cells >= (1ll << 31) || k.sumT >= (1ll << 31)) return fail(c, LASR_EINVAL, "band lattice of %lld cells is too large", k.cells);
-    return LASR_OK;
-}
-// tables (with the windows k.lo) -> device, one copy; tok may be null (lasr_lattice_band_dp: no labels are read).  img: the caller's,
-// alive until the stream has passed the copy
-int lat_band_upload(lasr_ctx* c, lasr_ctx::Lattice& w, LatBandCall& k, const int32_t* tok, std::vector<long long>& img) {
-    const int n = k.n;
-    // image (8-byte units): off [n + 1], bp_off [n], then the int arrays T, U, W, slot, tok_off, lo_off [n] each, tok [sum U], lo [sum T]
-    const size_t n_ints = 6 * (size_t)n + (size_t)k.sumU + (size_t)k.sumT;
-    img.assign((size_t)2 * n + 1 + (n_ints + 1) / 2, 0);
-    memcpy(img.data(), k.off.data(), sizeof(long long) * (n + 1));
-    memcpy(img.data() + n + 1, k.bp_off.data(), sizeof(long long) * n);
-    int* ip = (int*)(img.data() + 2 * n + 1);
-    const std::vector<int>* cols[6] = {&k.T, &k.U, &k.W, &k.slot, &k.tok_off, &k.lo_off};
-    for (int j = 0; j < 6; ++j) memcpy(ip + (size_t)j * n, cols[j]->data(), sizeof(int) * n);
-    if (tok && k.sumU) memcpy(ip + 6 * (size_t)n, tok, sizeof(int) * (size_t)k.sumU);
-    memcpy(ip + 6 * (size_t)n + k.sumU, k.lo.data(), sizeof(int) * (size_t)k.sumT);
-    RC(ensure_buf(c, &w.tab, &w.tab_n, img.size()));
-    HIPCHK(c, hipMemcpyAsync(w.tab, img.data(), sizeof(long long) * img.size(), hipMemcpyHostToDevice, c->stream));
-    const long long* dl = (const long long*)w.tab;
-    const int* di = (const int*)(dl + 2 * n + 1);
-    k.tab.tb = LatTab{dl, di, di + n, di + 3 * (size_t)n, di + 4 * (size_t)n, di + 6 * (size_t)n, n};
-    k.tab.W = di + 2 * (size_t)n; k.tab.lo_off = di + 5 * (size_t)n; k.tab.lo = di + 6 * (size_t)n + k.sumU;
-    k.d_bp_off = dl + n + 1;
-    return LASR_OK;
-}
-
-// k_lat_dp_band over the band lattices b / e (device) of call k; results stay in the workspace
-int lat_band_run_dp(lasr_ctx* c, lasr_ctx::Lattice& w, const LatBandCall& k, const float* b, const float* e, bool vit, bool want_frames,
+// k_lat_dp_band over the band lattices b / e (device) of call k (W set); results stay in the workspace
+int lat_band_run_dp(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const float* b, const float* e, bool vit, bool want_frames,
                     bool want_logps) {
-    RC(ensure_buf(c, &w.res, &w.res_n, (size_t)2 * k.n));
-    if (vit) {
-        RC(ensure_buf(c, &w.frames, &w.frames_n, (size_t)std::max(k.sumU, 1ll)));
-        RC(ensure_buf(c, &w.logps, &w.logps_n, (size_t)std::max(k.sumU, 1ll)));
-        if (k.bp_words) RC(ensure_buf(c, &w.bp, &w.bp_n, (size_t)k.bp_words));
-    }
+    RC(lat_dp_workspace(c, w, k, vit));
     LatBandDpArgs a{};
-    a.b = b; a.e = e; a.off = k.tab.tb.off; a.T = k.tab.tb.T; a.U = k.tab.tb.U; a.W = k.tab.W; a.lo_off = k.tab.lo_off; a.lo = k.tab.lo;
-    a.tok_off = k.tab.tb.tok_off;
+    a.b = b; a.e = e; a.off = k.tab.off; a.T = k.tab.T; a.U = k.tab.U; a.W = k.tab.W; a.lo_off = k.tab.lo_off; a.lo = k.tab.lo;
+    a.tok_off = k.tab.tok_off;
     a.loglik = w.res; a.viterbi = vit ? w.res + k.n : nullptr;
     a.frames = vit && want_frames ? w.frames : nullptr; a.logps = vit && want_logps ? w.logps : nullptr;
-    a.bp = w.bp; a.bp_off = k.d_bp_off;
+    a.bp = w.bp; a.bp_off = k.tab.bp_off;
     a.w_max = k.Wmax; a.vit = vit ? 1 : 0; a.lds_bp_words = vit ? k.lds_bp_words : 0;
     const size_t lds = sizeof(double) * (vit ? 4 : 2) * (size_t)a.w_max + sizeof(unsigned) * (size_t)a.lds_bp_words;
     if (k.Wmax <= 256) hipLaunchKernelGGL(k_lat_dp_band<1>, dim3(k.n), dim3(256), lds, c->stream, a);
@@ -245,11 +143,11 @@ int lat_band_run_dp(lasr_ctx* c, lasr_ctx::Lattice& w, const LatBandCall& k, con
 }
 
 // the banded inputs and outputs of lasr_align_band_* beside lasr_align_*'s
-struct LatBandIO { int band, max_passes; const int32_t* lo_in; int32_t* lo_out; int32_t* passes; int32_t* touch; LatBandCall* plan; };
+struct LatBandIO { int band, max_passes; const int32_t* lo_in; int32_t* lo_out; int32_t* passes; int32_t* touch; LatCall* plan; };
 
 // widths and first windows of a lasr_align_band_* call from its frame counts (host only; nothing has changed when it fails)
 int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io) {
-    LatBandCall& k = *io.plan;
+    LatCall& k = *io.plan;
     if (io.band < 1 || io.max_passes < 1) return fail(c, LASR_EINVAL, "band = %d, max_passes = %d (both >= 1)", io.band, io.max_passes);
     k.n = n;
     k.T.assign(T, T + n); k.U.assign(U, U + n); k.W.resize(n);
@@ -258,7 +156,7 @@ int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatB
         if (k.W[i] > LAT_BAND_WMAX)
             return fail(c, LASR_EINVAL, "utterance %d: a window of %d labels (at most %d; a single frame needs U + 1)", i, k.W[i], LAT_BAND_WMAX);
     }
-    RC(lat_band_layout(c, k));
+    RC(lat_layout_checked(c, k));
     k.lo.resize((size_t)k.sumT);
     for (int i = 0; i < n; ++i) {
         int32_t* lo = k.lo.data() + k.lo_off[i];
@@ -273,37 +171,25 @@ int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatB
 // every utterance through the joint and the banded dynamic programme; between passes the best paths come to the host and
 // lasr_band_windows' routine recentres the windows.  The loop ends when no utterance touches, no window changed, or at max_passes.
 int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io) {
-    LatBandCall& k = *io.plan;
-    const int M = c->M, J = c->d.joint, V = c->d.vocab;
+    LatCall& k = *io.plan;
     lasr_ctx::Lattice& w = c->lat;
     k.slot.assign(slots, slots + n);
     lat_mark(c, w, 1);
-    int Ml = 0;
-    for (int i = 0; i < n; ++i) Ml = std::max(Ml, slots[i] + 1);
-    RC(ensure_buf(c, &w.pp, &w.pp_n, (size_t)(k.Umax + 1) * Ml * J));
-    RC(ensure_buf(c, &w.ja, &w.ja_n, (size_t)LAT_R * J * c->esz));
-    RC(ensure_buf(c, &w.logits, &w.logits_n, (size_t)LAT_R * V));
-    RC(ensure_buf(c, &w.b, &w.b_n, (size_t)k.cells));
-    RC(ensure_buf(c, &w.e, &w.e_n, (size_t)k.cells));
+    const int Ml = lat_rows(slots, n);
+    RC(lat_workspace(c, w, k.Umax, Ml, k.cells));
     DecView v = sync_view(c, 1);
     RC(lat_teacher_force(c, w, v, slots, n, k.U, k.Umax, tokens, Ml));
     lat_mark(c, w, 2);
     const bool loop = io.max_passes > 1, path = loop || io.touch;
     const bool vit = o.viterbi || o.frames || o.logps || path;
-    std::vector<long long> img;
+    TabImage img;
     std::vector<int32_t> fr((size_t)std::max(k.sumU, 1ll)), lo_new((size_t)k.sumT), touch(n, 0);
     std::vector<double> res((size_t)2 * n);
     int passes = 0;
     for (;;) {
-        RC(lat_band_upload(c, w, k, tokens, img));
-        for (long long cell0 = 0; cell0 < k.cells; cell0 += LAT_R) {
-            const int nr = (int)std::min<long long>(LAT_R, k.cells - cell0);
-            hipLaunchKernelGGL(k_lat_ja_band, dim3(nr), dim3(256), 0, c->stream, (const float*)c->pe_sync, (const float*)w.pp, k.tab, cell0, nr,
-                               (void*)w.ja, J, M, Ml, LAT_R / 16, c->bf);
-            launch_logits_from(c, v, w.ja, LAT_R / 16, LAT_R, w.logits, nr);
-            hipLaunchKernelGGL(k_lat_pick_band, dim3((nr + 3) / 4), dim3(256), 0, c->stream, (const float*)w.logits, k.tab, cell0, nr, V,
-                               c->d.blank, w.b, w.e);
-        }
+        lat_pack(k, tokens, img);                     // (the windows k.lo are the pass's)
+        RC(lat_upload(c, w, img));
+        lat_blocks(c, w, v, LatBandMap{k.tab}, k.cells, Ml);
         lat_mark(c, w, 3);
         RC(lat_band_run_dp(c, w, k, w.b, w.e, vit, o.frames || path, o.logps != nullptr));
         lat_mark(c, w, 4);
@@ -327,20 +213,8 @@ int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens,
         if (!any_touch || !changed || passes >= io.max_passes) break;
         k.lo.swap(lo_new);
     }
-    // ---- the slots go back to fresh state (what lasr_stream_reset(.., 1 | 2 | 4) leaves)
-    RC(cmd_begin(c));
-    for (int i = 0; i < n; ++i) c->hc.what[slots[i]] = 7;
-    RC(cmd_commit(c));
-    RC(apply_reset(c, sync_view(c, c->la_sync), true));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    c->cmd_inflight = 0;
-    HIPCHK(c, hipMemcpy(o.loglik, w.res, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (o.viterbi) HIPCHK(c, hipMemcpy(o.viterbi, w.res + n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (o.frames && k.sumU) HIPCHK(c, hipMemcpy(o.frames, w.frames, sizeof(int) * (size_t)k.sumU, hipMemcpyDeviceToHost));
-    if (o.logps && k.sumU) HIPCHK(c, hipMemcpy(o.logps, w.logps, sizeof(float) * (size_t)k.sumU, hipMemcpyDeviceToHost));
-    if (o.blank_lp) HIPCHK(c, hipMemcpy(o.blank_lp, w.b, sizeof(float) * (size_t)k.cells, hipMemcpyDeviceToHost));
-    if (o.emit_lp) HIPCHK(c, hipMemcpy(o.emit_lp, w.e, sizeof(float) * (size_t)k.cells, hipMemcpyDeviceToHost));
+    RC(lat_release(c, slots, n));
+    RC(lat_copy_out(c, w, k, o));
     if (io.lo_out) memcpy(io.lo_out, k.lo.data(), sizeof(int32_t) * (size_t)k.sumT);
     for (int i = 0; i < n; ++i) {
         if (io.passes) io.passes[i] = passes;

@@ -7,7 +7,7 @@
 // index; a candidate contributes one label per depth, so the position adds nothing).  What the device side relies on follows:
 //   * parent[v] < v                              a node's predecessor is computed before it in node order
 //   * depth is non-decreasing                    the nodes of one depth are one contiguous range (k_lat_dp_tree's diagonal)
-//   * the children of a node are contiguous      k_lat_pick_tree walks [child_lo, child_lo + child_n)
+//   * the children of a node are contiguous      LatTreeMap's pick walks [child_lo, child_lo + child_n)
 // term[j] is the node of candidate j: duplicates share a node, an empty candidate maps to node 0.
 #pragma once
 

@@ -2,6 +2,9 @@
 from: both recursions against brute-force enumeration of every path, the tie rule, U = 0, and their relation to the numpy oracle's
 greedy decode.  Also: the new calls are bound and exposed."""
 import inspect
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -28,6 +31,20 @@ def test_symbols_and_python_surface():
     for meth in ("lasr_align_pcm", "lasr_align_feats", "lasr_lattice_dp"):
         assert hasattr(lib, meth)
     assert lib.lasr_lattice_dp(None, None, None, None, None, 1, None, None, None) == N.LASR_EINVAL      # no context: an error code
+
+
+def test_lattice_tables_under_asan_ubsan(tmp_path):
+    """Layout and table image of the full, banded and tree lattice (lasr_lattice_tables.hip.h, standard C++): every device view inside
+    the image, none overlapping, aligned, reading back its input; offsets against formulas written out in the program."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is part of the image"
+    exe = str(tmp_path / "lattice_tables_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", os.path.join(root, "tests", "c", "lattice_tables_check.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "lattice_tables_check: ok" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
 
 
 def brute(b, e, U):
