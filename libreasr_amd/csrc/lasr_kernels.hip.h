@@ -215,7 +215,8 @@ inline __global__ void k_reset_rows(const ResetArgs a) {
     if (wh & 2) {
         for (int l = 0; l < a.Lp; ++l) {
             act_st(a.bf, a.pred_h[l], (size_t)rp * a.H + u, bos ? a.bos_h[l][u] : a.pred_h0[l][u]);
-            if (a.pred_lstm) a.pred_c[l][(size_t)u * (W > 1 ? a.Md : a.M) + rp] = bos ? a.bos_c[l][u] : a.pred_c0[l][u];
+            // (unit-major over the Md decoder rows whatever W says: an op-level reset addresses plain rows of a beam context)
+            if (a.pred_lstm) a.pred_c[l][(size_t)u * a.Md + rp] = bos ? a.bos_c[l][u] : a.pred_c0[l][u];
         }
         if (bos)
             for (int j = u; j < a.J; j += a.H) a.pp[(size_t)rp * a.J + j] = a.bos_pp[j];

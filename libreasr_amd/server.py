@@ -475,7 +475,7 @@ class Scheduler(threading.Thread):
 
     def _take(self):
         """(cv held) One frame of every stream that can go now.  Returns (slots whose frame only fills the window / Buffer, slots
-        whose frame completes a model step, [(stream, frame)] of the generic form); the frames of the fused path are taken by
+        whose frame completes a model step, [(stream, frame, result cell)] of the generic form); the frames of the fused path are taken by
         _gather."""
         d = self.eng.desc
         qn, fast = self.qn, self.fast
@@ -491,7 +491,11 @@ class Scheduler(threading.Thread):
                         fast[i] = True
                         self.n_slow -= 1
                         continue
-                gen.append((s, s.inq.popleft()))
+                # the frame's result cell is queued as the frame is taken: an EOF marker handled below, in this same tick, then
+                # waits behind it (put later, by _submit_generic, the cell let EOF overtake the stream's last result)
+                cell = []
+                s.results.append(cell)
+                gen.append((s, s.inq.popleft(), cell))
                 qn[i] -= 1
                 self.n_wait -= 1
                 has[i] = qn[i] > 0
@@ -705,9 +709,7 @@ class Scheduler(threading.Thread):
     def _submit_generic(self, gen, d):
         """api-server.py:85-99: window of the last 3 frames, resampled + transformed per call (lasr_step_window, synchronous)."""
         groups = collections.OrderedDict()
-        for s, (pcm, sr) in gen:
-            cell = []
-            s.results.append(cell)
+        for s, (pcm, sr), cell in gen:
             s.frames.append(pcm)
             if len(s.frames) != d.n_window:
                 cell.append(None)

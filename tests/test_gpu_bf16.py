@@ -76,6 +76,9 @@ def test_bf16_ops(name):
         e = np.abs(hp[r] - x[0]).max()
         assert e < 0.06, f"predictor row {r}: {e}"
     # joint on given inputs: one GEMM -> tanh -> GEMM deep
+    # (the sharp check of these one-stage quantities -- pp, pe, logits, lp, the predictor's h and BN(h), x0 and the cell state of
+    #  encoder layer 0, element by element against a float64 model with a derived bound -- is test_gpu_bf16_exact.py; the
+    #  tolerances here are the coarse ones of round 2 and stay as they are)
     rng = np.random.default_rng(0)
     a = rng.standard_normal((5, H)).astype(np.float32)
     b = rng.standard_normal((5, H)).astype(np.float32)

@@ -13,6 +13,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bf16_exact as X
 import lattice_band_ref as B
 import lattice_ref as R
 from libreasr_amd import _native as N
@@ -347,7 +348,8 @@ def test_beam_context_is_refused():
 
 # ------------------------------------------------------------------------------- (f) bf16 context
 def test_bf16_context():
-    """structure only, as test_gpu_lattice.test_bf16_context"""
+    """the first frame's first label row within the bound of tests/bf16_exact.py, the rest structure only, as
+    test_gpu_lattice.test_bf16_context (row 0 of the band layout starts at label 0)"""
     eng = make("tiny", dtype="bf16")
     try:
         ys = transcripts("tiny", "rand40")
@@ -359,6 +361,8 @@ def test_bf16_context():
         assert w == 6 and r["blank_lp"].shape == (T, w) and r["emit_lp"].shape == (T, w) and r["lo"].shape == (T,)
         assert B.valid(T, U, w, r["lo"]) and 1 <= r["passes"] <= 4 and r["touch"] in (0, 1)
         assert np.all(np.isfinite(r["blank_lp"])) and np.all(np.isfinite(r["emit_lp"]))
+        assert r["lo"][0] == 0
+        X.check_first_cell("tiny", feats_all()[i][0], r["blank_lp"][0, 0], {y[0]: r["emit_lp"][0, 0]} if U else {}, f"bf16 band utterance {i}")
         assert r["viterbi"] <= r["loglik"] + 1e-9
         if np.isfinite(r["viterbi"]):                                     # the windows connect
             assert np.isfinite(r["loglik"])

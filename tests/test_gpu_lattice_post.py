@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bf16_exact as X
 import lattice_post_ref as P
 import lattice_ref as R
 from libreasr_amd import _native as N
@@ -294,15 +295,17 @@ def test_beam_context_is_refused():
 
 # ------------------------------------------------------------------------------- (e) bf16 context
 def test_bf16_context():
-    """bf16 values are not bounded in this project: structure and the sum invariants (the recursions are double whatever the operands)"""
+    """the first frame's first label row within the bound of tests/bf16_exact.py (as, and as loose as, in
+    test_gpu_lattice.test_bf16_context); beyond it structure and the sum invariants (the recursions are double whatever the operands)"""
     eng = make("tiny", dtype="bf16")
     try:
         ys = transcripts("tiny", "greedy")
         res = eng.align_feats(SLOTS, feats_all(), ys, lattice=True, posteriors=True)
     finally:
         eng.close()
-    for r, y in zip(res, ys):
+    for i, (r, y) in enumerate(zip(res, ys)):
         T, U = r["blank_lp"].shape[0], len(y)
+        X.check_first_cell("tiny", feats_all()[i][0], r["blank_lp"][0, 0], {y[0]: r["emit_lp"][0, 0]} if U else {}, f"bf16 post utterance {i}")
         assert r["occ_blank"].shape == (T, U + 1) and r["occ_emit"].shape == (T, U + 1)
         for k in POST_KEYS:
             assert r[k].shape[0] == (T if k.startswith("occ") else U) and np.all(np.isfinite(r[k])), k

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import bf16_exact as X
 import lattice_ref as R
 import lattice_tree_ref as TR
 from libreasr_amd import _native as N
@@ -328,8 +329,9 @@ def test_beam_context_is_refused():
 
 # ------------------------------------------------------------------------------- (f) bf16 context
 def test_bf16_context():
-    """No bound for continuous bf16 values exists in this project yet: structure only; the distance to the oracle's operand="bf16"
-    emulation is printed (DESIGN 5.4 records it)."""
+    """The root's row on the first frame (blank, and the emission into every child of the root) within the bound of
+    tests/bf16_exact.py, as -- and as loose as -- in test_gpu_lattice.test_bf16_context; beyond it structure only; the distance to
+    the oracle's operand="bf16" emulation is printed (DESIGN 5.4 records it)."""
     cands = candidates("tiny")
     eng = make("tiny", dtype="bf16", max_streams=32)
     try:
@@ -342,6 +344,9 @@ def test_bf16_context():
         assert np.all(np.isfinite(r["loglik"])) and np.all(np.isfinite(r["viterbi"]))
         assert np.all(r["viterbi"] <= r["loglik"] + 1e-9)
         assert r["loglik"][0] == r["loglik"][1] and r["viterbi"][0] == r["viterbi"][1]
+        tree = r["tree"]
+        kids = {int(tree["label"][v]): r["emit_lp"][0, v] for v in range(1, len(tree["parent"])) if tree["parent"][v] == 0}
+        X.check_first_cell("tiny", feats_all()[i][0], r["blank_lp"][0, 0], kids, f"bf16 tree utterance {i}")
         dt = dl = 0.0
         for j, (y, b, e, ll, vit) in enumerate(per):
             gb, ge = gathered(r, j)

@@ -780,3 +780,35 @@ def test_early_verdict_buffers_follow_the_depth_and_a_short_buffer_is_not_fatal(
         assert getattr(eng, "peek_efull", 0) >= 1 and sched._peek_cap > 0     # the overflow happened and the buffer grew
     finally:
         sched.shutdown()
+
+
+def test_eof_waits_behind_the_last_window_of_a_generic_stream():
+    """A client of another frame length (the window form, lasr_step_window) whose last frame and EOF marker reach the scheduler in
+    the same tick: the last window's result -- here the engine's refusal of a window too short to transform -- comes before EOF,
+    so the servicer sees it (EOF used to overtake it and the RPC ended without the error)."""
+    class Eng(FakeEngine):
+        def step_window(self, slots, windows, sr=16000):
+            self._own()
+            raise ValueError("window too short")
+
+    eng = Eng()
+    sched = srv.Scheduler(eng, depth=4)
+    sched.start()
+    try:
+        st = sched.open()
+        gate = threading.Event()              # hold the scheduler thread until the three frames and the marker are all queued
+        holder = threading.Thread(target=lambda: sched._call(lambda: gate.wait(10)))
+        holder.start()
+        time.sleep(0.05)
+        for _ in range(3):
+            sched.push_nowait(st, np.zeros(3, np.float32))               # 3 samples, not the engine's chunk of 4: the window form
+        sched.push_eof(st)
+        gate.set()
+        holder.join(timeout=10)
+        got = [st.outq.get(timeout=10) for _ in range(4)]
+        assert got[0] is None and got[1] is None
+        assert isinstance(got[2], ValueError), got
+        assert got[3] is srv.EOF
+        sched.close(st)
+    finally:
+        sched.shutdown()
