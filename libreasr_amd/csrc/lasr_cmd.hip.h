@@ -11,16 +11,17 @@ void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_sl
     const float* lg = (const float*)c->logits;
     // one wave per hypothesis row (k_beam_select_rw; V <= 2048 is checked at lasr_create for beam > 1)
     // (b.rec: per-token records, lasr_set_beam_records -- an instantiation of their own, so "off" runs the kernel it always ran)
-    if (b.rec) {
-        if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, true>), dim3(M), dim3(128), 0, v.stream, lg, b, iter_slot);
-        else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, true>), dim3(M), dim3(256), 0, v.stream, lg, b, iter_slot);
-        else hipLaunchKernelGGL((k_beam_select_rw<8, true>), dim3(M), dim3(512), 0, v.stream, lg, b, iter_slot);
-    } else if (c->W <= 2) hipLaunchKernelGGL((k_beam_select_rw<2, false>), dim3(M), dim3(128), 0, v.stream, lg, b, iter_slot);
-    else if (c->W <= 4) hipLaunchKernelGGL((k_beam_select_rw<4, false>), dim3(M), dim3(256), 0, v.stream, lg, b, iter_slot);
-    else hipLaunchKernelGGL((k_beam_select_rw<8, false>), dim3(M), dim3(512), 0, v.stream, lg, b, iter_slot);
+    with_const<0, 1>(b.rec ? 1 : 0, [&](auto rec) {
+        with_const<2, 4, 8>(c->W, [&](auto wt) {
+            constexpr int WT = decltype(wt)::value;
+            hipLaunchKernelGGL((k_beam_select_rw<WT, decltype(rec)::value != 0>), dim3(M), dim3(64 * WT), 0, v.stream, lg, b, iter_slot);
+        });
+    });
     if (c->lm.on)
-        LAUNCH_BEAM_FUSE(c->d.vocab, dim3(c->Md), dim3(256), 0, v.stream, (const float*)c->logits, b, iter_slot, (const float*)c->lm.lmz[lp], (const int*)c->lm.valid[lp],
-                           c->lm.alpha, c->lm.theta, c->lm.min_val);
+        with_const<8, 16>(keep16(c->d.vocab) ? 16 : 8, [&](auto keep) {
+            hipLaunchKernelGGL(k_beam_fuse<decltype(keep)::value>, dim3(c->Md), dim3(256), 0, v.stream, lg, b, iter_slot, (const float*)c->lm.lmz[lp],
+                               (const int*)c->lm.valid[lp], c->lm.alpha, c->lm.theta, c->lm.min_val);
+        });
 }
 
 // What `enqueue()` puts on stream `st`, as an instantiated graph: the one capture sequence of the library (the encoder's cell graphs,

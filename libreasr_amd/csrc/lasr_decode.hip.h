@@ -216,6 +216,8 @@ void decode_iteration(lasr_ctx* c, DecView& v, const DecState& s, BeamState* b, 
     launch_ppj(c, v, beam);
     if (!side) launch_lm(c, v, beam);
 }
+// the round protocol of the continuous loop, the same for the greedy and the beam state (host_flag: set per launch, cont_enqueue)
+ContRound cont_round_state(lasr_ctx* c) { return ContRound{1, c->c_iter, c->c_done, c->c_behind, nullptr, c->c_hcur_dev}; }
 // the beam's kernel state: synchronous / offline steps (trellis and records of the step), or cont = the continuous loop (rings)
 BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
     BeamState b{};
@@ -228,9 +230,9 @@ BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
         b.rec = c->beam_rec_on ? c->b_rec : nullptr;
         return b;
     }
-    b.iters = c->c_iters; b.trellis = c->b_tre_dev; b.unfinished = c->c_behind;
-    b.cont = 1; b.tring = lasr_ctx::TRING; b.frame_done = c->b_fdone_dev; b.iter_ctr = c->c_iter; b.done_blocks = c->c_done;
-    b.host_cur = c->c_hcur_dev; b.step_T = c->d.n_buffer; b.end_slots = lasr_ctx::ENDSLOTS;
+    static_cast<ContRound&>(b) = cont_round_state(c);
+    b.iters = c->c_iters; b.trellis = c->b_tre_dev;
+    b.tring = lasr_ctx::TRING; b.frame_done = c->b_fdone_dev; b.step_T = c->d.n_buffer; b.end_slots = lasr_ctx::ENDSLOTS;
     b.end_score = c->b_endsc_dev; b.end_alive = c->b_endal_dev;
     b.rec = c->beam_rec_on ? c->b_rec_ring_dev : nullptr;
     return b;

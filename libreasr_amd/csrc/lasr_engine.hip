@@ -1253,12 +1253,11 @@ int lasr_max_inflight(const lasr_ctx* c) {
 static void cont_states(lasr_ctx* c, const DecView& v, DecState& s, BeamState& bs) {
     const int M = c->M;
     s = c->ds;
-    s.t_idx = c->c_cur; s.iters = c->c_iters; s.step_ntok = c->c_ntotal; s.step_tok = c->c_tok_ring;
-    s.tok_cap = lasr_ctx::TOKRING; s.unfinished = c->c_behind; s.cont = 1; s.host_cur = c->c_hcur_dev;
+    static_cast<ContRound&>(s) = cont_round_state(c);
+    s.t_idx = c->c_cur; s.iters = c->c_iters; s.step_ntok = c->c_ntotal; s.step_tok = c->c_tok_ring; s.tok_cap = lasr_ctx::TOKRING;
     s.step_frame = c->align_on ? c->c_frame_ring : nullptr; s.step_logp = c->align_on ? c->c_logp_ring : nullptr;
     s.host_ntot = c->tr_on ? c->c_hcur_dev + M : nullptr;
-    s.ntok_end = c->c_ntok_end; s.step_T = c->d.n_buffer; s.end_slots = lasr_ctx::ENDSLOTS; s.done_blocks = c->c_done;
-    s.iter_ctr = c->c_iter;
+    s.ntok_end = c->c_ntok_end; s.step_T = c->d.n_buffer; s.end_slots = lasr_ctx::ENDSLOTS;
     s.dbg = c->dbg ? c->dbg + ((size_t)4 * 4096 + 4095) * 16 : nullptr;
     bs = c->W > 1 ? beam_state(c, v, true, c->d.max_iters_stream) : BeamState{};
 }
@@ -2442,22 +2441,49 @@ static int lm_side_setup(lasr_ctx* c) {
     return LASR_OK;
 }
 
-int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights) {
+// What attaching an LM in either form starts with: the argument checks (q8: those of the int8-served form), an idle, synchronised
+// context, and the fields of c->lm both forms share
+static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights, bool q8) {
     if (!c) return LASR_EINVAL;
     if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
+    if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)
         return fail(c, LASR_EINVAL, "LM weight blob has %zu floats, expected %zu", n_weights, d ? lasr_lm_weight_count(d) : (size_t)0);
     if (d->vocab != c->d.vocab) return fail(c, LASR_EINVAL, "LM vocabulary %d != model vocabulary %d", d->vocab, c->d.vocab);
-    if (d->vocab > 4096) return fail(c, LASR_EINVAL, "LM fusion keeps a row's log-probs in registers: vocab <= 4096");
-    if (d->embed % 16 || d->hidden % (c->bf ? 32 : 16)) return fail(c, LASR_EINVAL, "LM dims must be multiples of 16 (hidden: 32 for bf16)");
+    if (!q8) {
+        if (d->vocab > 4096) return fail(c, LASR_EINVAL, "LM fusion keeps a row's log-probs in registers: vocab <= 4096");
+        if (d->embed % 16 || d->hidden % (c->bf ? 32 : 16)) return fail(c, LASR_EINVAL, "LM dims must be multiples of 16 (hidden: 32 for bf16)");
+    } else {
+        if (d->vocab > 4096 || d->vocab % 16) return fail(c, LASR_EINVAL, "LM fusion keeps a row's log-probs in registers: vocab <= 4096, multiple of 16");
+        if (d->hidden % 4 || d->hidden > 1024 || d->embed > 1024 || d->embed < 1 || d->layers < 1 || d->layers > 8)
+            return fail(c, LASR_EINVAL, "int8 LM: hidden a multiple of 4, embed / hidden <= 1024 (exact integer accumulation), 1..8 layers");
+    }
     RC(flush_lazy(c));
     RC(require_idle(c));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     lasr_ctx::LM& m = c->lm;
+    m.E = d->embed; m.H = d->hidden; m.L = d->layers; m.alpha = d->alpha; m.theta = d->theta; m.min_val = d->min_val;
+    return LASR_OK;
+}
+// ... and ends with: the decode loop sees the LM
+static int lm_attach_finish(lasr_ctx* c, bool q8) {
+    lasr_ctx::LM& m = c->lm;
+    drop_decode_graphs(c);                                              // decode groups change shape
+    // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
+    //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
+    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la_stream = c->la_offline = c->la_sync = 1;
+    c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
+    m.q8 = q8;
+    m.on = true;
+    return lm_side_setup(c);
+}
+
+int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights) {
+    RC(lm_attach_begin(c, d, weights, n_weights, false));
+    lasr_ctx::LM& m = c->lm;
     const int V = d->vocab, E = d->embed, H = d->hidden, L = d->layers;
     const int M = c->Md;                               // LM rows: streams, or hypothesis slots with beam > 1 (Md = M x W)
-    m.E = E; m.H = H; m.L = L; m.alpha = d->alpha; m.theta = d->theta; m.min_val = d->min_val;
     Reader rd{weights, n_weights};
     const float* embed = rd.take((size_t)V * E);
     m.cells.resize(L);
@@ -2501,14 +2527,7 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
         }
         RC(dalloc0(c, &m.lmz[p], (size_t)M * V)); RC(dalloc0(c, &m.valid[p], M));
     }
-    drop_decode_graphs(c);                                              // decode groups change shape
-    // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
-    //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
-    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la_stream = c->la_offline = c->la_sync = 1;
-    c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
-    m.on = true;
-    RC(lm_side_setup(c));
-    return LASR_OK;
+    return lm_attach_finish(c, false);
 }
 
 // The LM as the reference serves it: load_lm (lm.py:86-100) runs maybe_quantize (utils.py:197-210) =
@@ -2517,22 +2536,9 @@ int lasr_attach_lm(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, siz
 // row and per matmul (at run time the quantised image of every h is made once, by the cell kernel that produces it: k_lm_cell_q).  Numerics of the installed torch's x86 / fbgemm engine (restated in
 // oracle/rnnt_oracle.py:dq_linear and pinned to the reference's quantised LM there).
 int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights) {
-    if (!c) return LASR_EINVAL;
-    if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
-    if (c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
-    if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)
-        return fail(c, LASR_EINVAL, "LM weight blob has %zu floats, expected %zu", n_weights, d ? lasr_lm_weight_count(d) : (size_t)0);
-    if (d->vocab != c->d.vocab) return fail(c, LASR_EINVAL, "LM vocabulary %d != model vocabulary %d", d->vocab, c->d.vocab);
-    if (d->vocab > 4096 || d->vocab % 16) return fail(c, LASR_EINVAL, "LM fusion keeps a row's log-probs in registers: vocab <= 4096, multiple of 16");
-    if (d->hidden % 4 || d->hidden > 1024 || d->embed > 1024 || d->embed < 1 || d->layers < 1 || d->layers > 8)
-        return fail(c, LASR_EINVAL, "int8 LM: hidden a multiple of 4, embed / hidden <= 1024 (exact integer accumulation), 1..8 layers");
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    RC(lm_attach_begin(c, d, weights, n_weights, true));
     lasr_ctx::LM& m = c->lm;
     const int V = d->vocab, E = d->embed, H = d->hidden, L = d->layers, M = c->M;
-    m.E = E; m.H = H; m.L = L; m.alpha = d->alpha; m.theta = d->theta; m.min_val = d->min_val;
     auto pad32 = [](int k) { return (k + 31) / 32 * 32; };
     m.Kp_h = pad32(H);
     Reader rd{weights, n_weights};
@@ -2601,15 +2607,7 @@ int lasr_attach_lm_int8(lasr_ctx* c, const lasr_lm_desc* d, const float* weights
     RC(dalloc(c, &m.gx, (size_t)M * 4 * H)); RC(dalloc(c, &m.gh, (size_t)M * 4 * H));
     RC(dalloc(c, &m.qa, (size_t)M * Kmax)); RC(dalloc(c, &m.sx, M));
     RC(dalloc(c, &m.raw, (size_t)M * V)); RC(dalloc0(c, &m.lmz[0], (size_t)M * V)); RC(dalloc0(c, &m.valid[0], M));
-    drop_decode_graphs(c);                                              // decode groups change shape
-    // (round 4: lookahead stays on with an LM -- blank frames change neither the predictor nor the LM state, k_select re-picks the
-    //  token of the first non-blank frame of its window; LASR_LM_LOOKAHEAD=0 restores one frame per iteration)
-    if (getenv("LASR_LM_LOOKAHEAD") && atoi(getenv("LASR_LM_LOOKAHEAD")) == 0) c->la_stream = c->la_offline = c->la_sync = 1;
-    c->ds.lmz = m.lmz[0]; c->ds.lm_valid = m.valid[0]; c->ds.lm_alpha = m.alpha; c->ds.lm_theta = m.theta; c->ds.lm_min = m.min_val;
-    m.q8 = true;
-    m.on = true;
-    RC(lm_side_setup(c));
-    return LASR_OK;
+    return lm_attach_finish(c, true);
 }
 
 // ---------------------------------------------------------------------------- stats / bench

@@ -40,41 +40,47 @@ __device__ __forceinline__ float sigmoid_(float x) { return 1.0f / (1.0f + expf(
 // ------------------------------------------------------------------------------------------------
 // small kernels
 // ------------------------------------------------------------------------------------------------
-// joint activation for all rows (start of a step): ja = tanh(pe[t_idx] + pp).
-// W > 1 (beam search): rows are hypothesis slots, W per stream; t_idx / T_row / pe are per stream (M_enc rows)
-inline __global__ void k_ja(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
-                     const int* __restrict__ T_row, void* __restrict__ ja, int J, int M, int MT, int ring, int bf,
-                     int W, int M_enc, int la) {
+// joint activation: ja = tanh(pe[(t + k) % ring] + pp) for the frames t .. t+la-1 a row may decide (rows k*M + r of ja; la = 1 but for
+// the greedy lookahead).  W > 1 (beam search): rows are hypothesis slots, W per stream; t_idx / pe and the frames-available
+// counts are per stream (M_enc rows).  avail(q): frames available to stream q; lim = false: no limit (and a null t_idx: frame
+// 0 -- the op-level joint).  avail_out: where the first row of a stream stores the count for the kernels behind this one.
+struct AvailV { int v[512]; };
+template <class Avail>
+__device__ __forceinline__ void ja_body(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
+                                        const Avail& avail, bool lim, int* __restrict__ avail_out, void* __restrict__ ja, int J,
+                                        int M, int MT, int ring, int bf, int W, int M_enc, int la) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= M * J) return;
     const int r = idx / J, j = idx - r * J;
     const int q = W > 1 ? r / W : r;
+    const int Tav = lim ? avail(q) : 0;
+    if (avail_out && j == 0 && r == q * W) avail_out[q] = Tav;
     const int t = t_idx ? t_idx[q] : 0;
     const float p = pp[(size_t)r * J + j];
-    for (int k = 0; k < la; ++k) {           // greedy lookahead: frames t .. t+la-1 (rows k*M + r); la = 1 otherwise
-        if (T_row && t + k >= T_row[q]) return;
+    for (int k = 0; k < la; ++k) {
+        if (lim && t + k >= Tav) return;
         act_st(bf, ja, act_off(bf, k * M + r, j, MT), tanhf(pe[((size_t)((t + k) % ring) * M_enc + q) * J + j] + p));
     }
 }
-
+// start of a step (and the op-level joint: null t_idx / T_row), frames available from an array
+inline __global__ void k_ja(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
+                     const int* __restrict__ T_row, void* __restrict__ ja, int J, int M, int MT, int ring, int bf,
+                     int W, int M_enc, int la) {
+    ja_body(pe, pp, t_idx, [&](int q) { return T_row[q]; }, T_row != nullptr, nullptr, ja, J, M, MT, ring, bf, W, M_enc, la);
+}
 // continuous greedy loop, admission of newly encoded steps (<= 512 rows): the rows' new "frames available" counts come BY
 // VALUE (the host knows every row's cumulative frame count), are stored for the kernels behind this one and used here for
 // the joint activation of the rows that were idle -- one launch instead of a counter-advance kernel per admitted step + k_ja
-struct AvailV { int v[512]; };
 inline __global__ void k_ja_admit(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
                            const AvailV av, int* __restrict__ avail_out, void* __restrict__ ja, int J, int M, int MT, int ring,
                            int bf, int la) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= M * J) return;
-    const int r = idx / J, j = idx - r * J;
-    const int Tav = av.v[r];
-    if (j == 0) avail_out[r] = Tav;
-    const int t = t_idx[r];
-    const float p = pp[(size_t)r * J + j];
-    for (int k = 0; k < la; ++k) {
-        if (t + k >= Tav) return;
-        act_st(bf, ja, act_off(bf, k * M + r, j, MT), tanhf(pe[((size_t)((t + k) % ring) * M + r) * J + j] + p));
-    }
+    ja_body(pe, pp, t_idx, [&](int q) { return av.v[q]; }, true, avail_out, ja, J, M, MT, ring, bf, 1, M, la);
+}
+// continuous beam loop, the same admission (<= 512 streams): every hypothesis slot of the streams that have a frame to decode
+inline __global__ void k_ja_admit_beam(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
+                                const AvailV av, int* __restrict__ avail_out, void* __restrict__ ja, int J, int Md, int W, int M_enc,
+                                int MT, int ring, int bf) {
+    ja_body(pe, pp, t_idx, [&](int q) { return av.v[q]; }, true, avail_out, ja, J, Md, MT, ring, bf, W, M_enc, 1);
 }
 
 // fragment-major -> row-major [rows][K] f32
@@ -223,8 +229,51 @@ inline __global__ void k_reset_rows(const ResetArgs a) {
     }
 }
 
+// The round protocol of the continuous loop (decode running across chunk boundaries, lasr_step_submit / _wait), the part of
+// DecState and BeamState the selection kernels share.  A round's number comes from a device counter, so a group of rounds is
+// launch-invariant and replays as a hipGraph; the last workgroup to arrive in the last round of a group publishes the "rows
+// still behind" count straight into pinned host memory (no copy kernel between the group and the host).
+struct ContRound {
+    int cont;          // 0: synchronous / offline step -- the caller names the slot of `unfinished`, the other fields are unused
+    int* iter_ctr;     // device round counter; the flag-ring slot is iter_ctr & 63
+    int* done_blocks;  // [64] ring of arrival counts
+    int* unfinished;   // [64] ring (cont = 0: [n_iter_slots]) rows / streams still decoding after the round
+    int* host_flag;    // pinned; nullptr: nothing to publish in this launch
+    int* host_cur;     // [M] pinned: the row's frame cursor, stored with the flag (the host derives "step j of row r is decoded"
+                       //     for EVERY step in flight from it: no per-step target upload)
+};
+struct ContSlot { int no, slot; };      // round number, slot of the flag rings
+// Start of a round, every thread: (number, slot); `first` (one thread of the launch) recycles the rings half a turn ahead.
+// owner: the launch advances iter_ctr when it is done (cont_arrive) and owns `unfinished`; a launch that is not the owner runs
+// behind the owner of the same round, which has moved the counter on by one, and only counts arrivals on a ring of its own.
+__device__ __forceinline__ ContSlot cont_round(const ContRound& s, int slot_in, int* arrivals, bool owner, bool first) {
+    if (!s.cont) return ContSlot{slot_in, slot_in};
+    const int no = (int)((*(const unsigned*)s.iter_ctr - (owner ? 0u : 1u)) & 0x3fffffffu);     // same value in every workgroup of the launch
+    const int slot = no & 63;
+    if (first) {
+        if (owner) s.unfinished[(slot + 32) & 63] = 0;
+        arrivals[(slot + 32) & 63] = 0;
+    }
+    return ContSlot{no, slot};
+}
+// End of a round, thread 0 of every workgroup after its last store of the launch.  publishes: this launch owns the host
+// publication -- the workgroup's stores to pinned memory are fenced before the count, and the last arrival releases
+// `unfinished` to host_flag at system scope (the host spins on that word).
+__device__ __forceinline__ void cont_arrive(const ContRound& s, ContSlot rd, int* arrivals, bool owner, bool publishes) {
+    if (!s.cont) return;
+    const bool pub = publishes && s.host_flag;
+    if (pub) __threadfence_system();
+    if (atomicAdd(&arrivals[rd.slot], 1) == (int)gridDim.x - 1) {      // last workgroup of the launch
+        if (pub) {
+            const int v = atomicAdd(&s.unfinished[rd.slot], 0);
+            __hip_atomic_store(s.host_flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        if (owner) *s.iter_ctr = rd.no + 1;
+    }
+}
+
 // per-step decode state
-struct DecState {
+struct DecState : ContRound {
     int* t_idx;        // [M] current encoder frame of the row inside this step
     int* iters;        // [M] joint evaluations done on the current frame
     int* token;        // [M] last emitted token (predictor input)
@@ -238,23 +287,12 @@ struct DecState {
     double* logp_sum;  // [M] sum of log p of every decision (models.py:420-422)
     int* sum_iters;    // [M] evaluations in this step
     int* n_ones;       // [M] frames finished after exactly one evaluation (alignment_score)
-    int* unfinished;   // [n_iter_slots] rows still decoding after iteration i
-    // continuous mode (decode loop running across chunk boundaries, lasr_step_submit/_wait):
-    //   t_idx = global frame cursor, T_row = frames available, step_ntok = tokens emitted so far,
-    //   step_tok = token ring of tok_cap entries per row
-    int cont;
-    int* host_cur;     // [M] pinned host memory: the row's frame cursor, stored by the last iteration of a group (the host
-                       //     derives "step j of row r is decoded" for EVERY step in flight from it: no per-step target upload)
+    // continuous mode (ContRound::cont): t_idx = global frame cursor, T_row = frames available, step_ntok = tokens emitted so
+    //   far, step_tok = token ring of tok_cap entries per row
     int* host_ntot;    // [M] pinned (diagnostics, may be nullptr): tokens emitted so far, stored with host_cur
     int* ntok_end;     // [M][end_slots] tokens emitted when row r finished its step j (slot j % end_slots)
     int step_T;        // frames per model step (n_buffer)
     int end_slots;
-    // continuous mode, last iteration of a group: the last workgroup to finish publishes the "rows still
-    // behind" count straight into pinned host memory (no copy kernel between the group and the host)
-    int* done_blocks;  // [64] ring, like unfinished
-    int* host_flag;    // nullptr: nothing to publish in this launch
-    int* iter_ctr;     // continuous mode: device-side iteration counter (the flag-ring slot is iter_ctr & 63), so
-                       // a group of iterations is launch-invariant and can be replayed as a hipGraph
     // LM shallow fusion (LMFuser.fuse, lm.py:59-79): standardised LM log-probs of the row's last token
     const float* lmz;  // [M][V] (nullptr: no LM attached)
     const int* lm_valid; // [M] the LM has advanced at least once since the last LM reset
@@ -443,6 +481,68 @@ inline __global__ void k_step_begin(DecState s, int M, int n_iter_slots, int res
     if (i < n_iter_slots) s.unfinished[i] = 0;
 }
 
+// ---- LMFuser arithmetic (lm.py:49-79, utils.py:162-164), shared by k_select's LM branch, k_lm_post and k_beam_fuse.  One
+// workgroup of 256 threads per row, V <= 256 KEEP: thread tid holds element tid + 256 q of the row in slot q.
+// lm_standardise: z[] = the row's raw values, (best, lse) = its maximum and log-sum-exp as the kernel took them.  Leaves the
+// standardised log-softmax in z[] -- log-softmax, subtract the mean (t.add_(-t.mean())), subtract the mean again as torch.std
+// does -- and returns den = unbiased std + 1e-5; entry 0 = MIN_VAL is the caller's.  Slots past V hold and contribute exact
+// zeros, so the result does not depend on KEEP.  sh4: 4 floats of LDS (block_sum_256 three times: six barriers).
+template <int KEEP>
+__device__ __forceinline__ float lm_standardise(float (&z)[KEEP], float best, float lse, int V, float* sh4, int tid) {
+    const int lane = tid & 63, w = tid >> 6;
+    float part = 0.f;
+#pragma unroll
+    for (int q = 0; q < KEEP; ++q) {
+        const int j = tid + 256 * q;
+        z[q] = j < V ? (z[q] - best) - lse : 0.f;
+        part += z[q];
+    }
+    const float mean = block_sum_256(part, sh4, lane, w) / (float)V;
+    part = 0.f;
+#pragma unroll
+    for (int q = 0; q < KEEP; ++q) {
+        const int j = tid + 256 * q;
+        z[q] = j < V ? z[q] - mean : 0.f;
+        part += z[q];
+    }
+    const float mean2 = block_sum_256(part, sh4, lane, w) / (float)V;
+    part = 0.f;
+#pragma unroll
+    for (int q = 0; q < KEEP; ++q) {
+        const int j = tid + 256 * q;
+        const float d = j < V ? z[q] - mean2 : 0.f;
+        part += d * d;
+    }
+    return sqrtf(block_sum_256(part, sh4, lane, w) / (float)(V - 1)) + 1e-5f;
+}
+// LMFuser.fuse's re-pick: argmax over j of alpha * lm[j] + theta * joint[j], joint = z[] / den with entry 0 = lm_min, products and
+// sum rounded separately (no FMA contraction).  amax_before is a total order on (value, index) and the indices are unique, so
+// the winner does not depend on the reduction tree: any wave reduction and any order of the 4-wave merge give the same token.
+// sv / si: 4 words of LDS each (may still be read from an earlier use: barrier first).  Every thread returns the token.
+template <int KEEP>
+__device__ __forceinline__ int lm_fused_argmax(const float (&z)[KEEP], float den, const float* __restrict__ lz, float alpha, float theta,
+                                               float lm_min, int V, float* sv, int* si, int tid) {
+    float fb = -INFINITY;
+    int fa = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < KEEP; ++q) {                 // ascending j per thread: the first maximum wins
+        const int j = tid + 256 * q;
+        if (j >= V) continue;
+        const float jo = j == 0 ? lm_min : z[q] / den;
+        const float f = __fadd_rn(__fmul_rn(alpha, lz[j]), __fmul_rn(theta, jo));
+        if (amax_gt(f, fb)) { fb = f; fa = j; }
+    }
+    wave_argmax_f32(fb, fa);
+    __syncthreads();
+    if ((tid & 63) == 0) { sv[tid >> 6] = fb; si[tid >> 6] = fa; }
+    __syncthreads();
+    fb = sv[0]; fa = si[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+        if (amax_before(sv[q], si[q], fb, fa)) { fb = sv[q]; fa = si[q]; }
+    return amax_index(fa, V);
+}
+
 // log-softmax + argmax over the vocabulary and the greedy state machine of
 // Transducer.decode_greedy / transcribe_stream (models.py:405-443, 530-571), one workgroup per row.
 // PLAIN: only (argmax, log p) are produced (op-level joint entry point).
@@ -476,23 +576,8 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
             zv[k][q] = j < V ? z[j] : -INFINITY;
         }
     }
-    const int iter_no = (!PLAIN && s.cont) ? (int)(*(const unsigned*)s.iter_ctr & 0x3fffffffu) : iter_slot_in;   // same value in every workgroup of the launch
-    const int iter_slot = (!PLAIN && s.cont) ? (iter_no & 63) : iter_slot_in;
-    if (!PLAIN && s.cont && r == 0 && tid == 0) {                                           // recycle the flag rings
-        s.unfinished[(iter_slot + 32) & 63] = 0;
-        s.done_blocks[(iter_slot + 32) & 63] = 0;
-    }
-    auto publish = [&]() {           // thread 0 of every workgroup, after its last store of this launch
-        if (PLAIN || !s.cont) return;
-        if (s.host_flag) __threadfence_system();     // this row's tokens / marks (pinned memory) before the count
-        if (atomicAdd(&s.done_blocks[iter_slot], 1) == (int)gridDim.x - 1) {      // last workgroup of the launch
-            if (s.host_flag) {
-                const int v = atomicAdd(&s.unfinished[iter_slot], 0);
-                __hip_atomic_store(s.host_flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            *s.iter_ctr = iter_no + 1;
-        }
-    };
+    const ContSlot rd = PLAIN ? ContSlot{iter_slot_in, iter_slot_in} : cont_round(s, iter_slot_in, s.done_blocks, true, r == 0 && tid == 0);
+    const int iter_slot = rd.slot;
     // state of the row (in flight together with the logits)
     int t = 0, Tr = 1, it_cur = 0, n0 = 0, si0 = 0, no0 = 0;
     double lp0 = 0.0;
@@ -505,7 +590,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
                     s.host_cur[r] = t;
                     if (s.host_ntot) s.host_ntot[r] = s.step_ntok[r];
                 }
-                publish();
+                cont_arrive(s, rd, s.done_blocks, true, true);
             }
             return;
         }
@@ -591,57 +676,9 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
 #pragma unroll
                 for (int q = 0; q < KEEP; ++q) zl[q] = zv[k][q];
             }
-        const float lse = logf(sumk);
-        float part = 0.f;
-#pragma unroll
-        for (int q = 0; q < KEEP; ++q) {
-            const int j = tid + 256 * q;
-            zl[q] = j < V ? (zl[q] - bestk) - lse : 0.f;        // log-softmax; padding contributes nothing
-            part += zl[q];
-        }
-        const float mean = block_sum_256(part, sh4, lane, w) / (float)V;
-        part = 0.f;
-#pragma unroll
-        for (int q = 0; q < KEEP; ++q) {
-            const int j = tid + 256 * q;
-            zl[q] = j < V ? zl[q] - mean : 0.f;                // t.add_(-t.mean())
-            part += zl[q];
-        }
-        const float mean2 = block_sum_256(part, sh4, lane, w) / (float)V;   // torch.std subtracts its own mean again
-        part = 0.f;
-#pragma unroll
-        for (int q = 0; q < KEEP; ++q) {
-            const int j = tid + 256 * q;
-            const float d = j < V ? zl[q] - mean2 : 0.f;
-            part += d * d;
-        }
-        const float sd = sqrtf(block_sum_256(part, sh4, lane, w) / (float)(V - 1));
-        const float den = sd + 1e-5f;
-        const float* lz = s.lmz + (size_t)r * V;
-        float fb = -INFINITY;
-        int fa = 0x7fffffff;
-#pragma unroll
-        for (int q = 0; q < KEEP; ++q) {
-            const int j = tid + 256 * q;
-            if (j >= V) continue;
-            const float jo = j == 0 ? s.lm_min : zl[q] / den;
-            const float f = __fadd_rn(__fmul_rn(s.lm_alpha, lz[j]), __fmul_rn(s.lm_theta, jo));   // no FMA contraction
-            if (amax_gt(f, fb)) { fb = f; fa = j; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(fb, o);
-            const int oa = __shfl_xor(fa, o);
-            if (amax_before(ob, oa, fb, fa)) { fb = ob; fa = oa; }
-        }
-        __syncthreads();
-        if (lane == 0) { sv[0][w] = fb; si[0][w] = fa; }
-        __syncthreads();
-        fb = sv[0][0]; fa = si[0][0];
-#pragma unroll
-        for (int q = 1; q < 4; ++q)
-            if (amax_before(sv[0][q], si[0][q], fb, fa)) { fb = sv[0][q]; fa = si[0][q]; }
-        tok_e = amax_index(fa, V);                          // the emitted token; log p stays the unfused one (models.py:422)
+        const float den = lm_standardise<KEEP>(zl, bestk, logf(sumk), V, sh4, tid);
+        // the emitted token; log p stays the unfused one (models.py:422)
+        tok_e = lm_fused_argmax<KEEP>(zl, den, s.lmz + (size_t)r * V, s.lm_alpha, s.lm_theta, s.lm_min, V, sv[0], si[0], tid);
     }
     // ---- the decisions, in frame order (models.py:405-443, 530-571): a row consumes its run of blank frames and, if it
     // comes, the first token after it.  Every thread tracks t and the per-frame evaluation count; thread 0 owns the rest.
@@ -694,24 +731,9 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
     }
     if (t < Tr) atomicAdd(&s.unfinished[iter_slot], 1);     // continuous mode: rows that still have encoded frames to decode
     if (dbgt) s.dbg[4] = wall_clock64();                          // state stored
-    publish();
+    cont_arrive(s, rd, s.done_blocks, true, true);                // (this row's tokens / marks are in pinned memory)
     if (dbgt) s.dbg[5] = wall_clock64();
 }
-// launch with the compile-time lookahead bound that covers `la`
-template <bool PLAIN>
-inline void launch_select(hipStream_t st, int rows, const float* logits, int V, int blank, int max_iters, const int* T_row,
-                          const DecState& s, int iter_slot, float* out_logp, int* out_arg, int la, int M) {
-    if (V <= 2048 && !s.lmz) {      // (the LM re-pick keeps the whole row in registers: 16 slots)
-        if (la <= 1) hipLaunchKernelGGL((k_select<PLAIN, 1, 8>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, 1, M);
-        else if (la == 2) hipLaunchKernelGGL((k_select<PLAIN, 2, 8>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, la, M);
-        else hipLaunchKernelGGL((k_select<PLAIN, 4, 8>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, la, M);
-        return;
-    }
-    if (la <= 1) hipLaunchKernelGGL((k_select<PLAIN, 1, 16>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, 1, M);
-    else if (la == 2) hipLaunchKernelGGL((k_select<PLAIN, 2, 16>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, la, M);
-    else hipLaunchKernelGGL((k_select<PLAIN, 4, 16>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot, out_logp, out_arg, la, M);
-}
-
 // LMFuser.advance (lm.py:49-53) for the rows that just emitted a token: log_softmax of the LM's output
 // layer, standardise (utils.py:162-164), entry 0 = MIN_VAL.  One workgroup per row, V <= 4096.
 // Beam search (W > 1): rows are hypothesis slots; a slot that was not extended takes the LM output of its PARENT slot from
@@ -753,30 +775,7 @@ __global__ __launch_bounds__(256) void k_lm_post(const float* __restrict__ raw, 
 #pragma unroll
     for (int q = 0; q < KEEP; ++q) part += expf(zv[q] - best);
     const float lse = logf(block_sum_256(part, sh4, lane, w));
-    part = 0.f;
-#pragma unroll
-    for (int q = 0; q < KEEP; ++q) {
-        const int j = tid + 256 * q;
-        zv[q] = j < V ? (zv[q] - best) - lse : 0.f;
-        part += zv[q];
-    }
-    const float mean = block_sum_256(part, sh4, lane, w) / (float)V;
-    part = 0.f;
-#pragma unroll
-    for (int q = 0; q < KEEP; ++q) {
-        const int j = tid + 256 * q;
-        zv[q] = j < V ? zv[q] - mean : 0.f;
-        part += zv[q];
-    }
-    const float mean2 = block_sum_256(part, sh4, lane, w) / (float)V;
-    part = 0.f;
-#pragma unroll
-    for (int q = 0; q < KEEP; ++q) {
-        const int j = tid + 256 * q;
-        const float d = j < V ? zv[q] - mean2 : 0.f;
-        part += d * d;
-    }
-    const float den = sqrtf(block_sum_256(part, sh4, lane, w) / (float)(V - 1)) + 1e-5f;
+    const float den = lm_standardise<KEEP>(zv, best, lse, V, sh4, tid);
     float* o = lmz + (size_t)r * V;
 #pragma unroll
     for (int q = 0; q < KEEP; ++q) {
@@ -911,7 +910,7 @@ inline __global__ __launch_bounds__(256) void k_lm_cell_q(const float* __restric
 // evaluated again unless the per-frame cap is reached.  When every slot is in B the stream moves to
 // the next frame.  W = 1 is exactly the greedy machine of k_select.
 // ------------------------------------------------------------------------------------------------
-struct BeamState {
+struct BeamState : ContRound {
     int W, V, blank, max_iters, Md;
     int* t_idx;        // [M] per stream
     int* iters;        // [M] rounds done on the current frame
@@ -923,20 +922,15 @@ struct BeamState {
     int* emit;         // [Md] 1 iff the slot was extended by a non-blank token in this round
     int* parent;       // [Md] slot (0..W-1) whose state this slot continues
     int* trellis;      // [n_iter_slots][Md]  (parent << 16) | (token + 1 if extended else 0); -1 stream idle, -2 dead slot
-    int* unfinished;   // [n_iter_slots]
     unsigned long long* dbg;   // LASR_DBG_TIMING: phase timestamps of workgroup 0 (wall_clock64, 10 ns ticks)
     // continuous mode (lasr_step_submit / lasr_step_wait with beam > 1): the selection loop keeps running across chunk boundaries,
     // every stream on its own frame cursor (rounds per model step = those the stream needs, not the maximum over the batch).
     //   t_idx = global frame cursor, T_row = frames available; the round's records go to slot (round % tring) of the pinned
     //   trellis ring, with a per-stream "frame finished in this round" word beside them; when a stream finishes a model step
     //   (cursor % step_T == 0) its slot scores / alive flags are stored for the host under the step's index.
-    int cont;
+    //   (ContRound: unfinished / host_flag count STREAMS with frames left, host_cur holds the streams' frame cursors)
     int tring;           // rounds in the trellis ring
     int* frame_done;     // [tring][M] pinned: 1 iff the stream finished its frame in that round
-    int* iter_ctr;       // device round counter (launch-invariant groups: hipGraph replay)
-    int* done_blocks;    // [64]
-    int* host_flag;      // last round of a group: "streams with frames left" goes here (pinned), else nullptr
-    int* host_cur;       // [M] pinned: frame cursors, stored with the flag
     int step_T, end_slots;
     double* end_score;   // [M][end_slots][W] pinned
     int* end_alive;      // [M][end_slots] pinned (bit j = slot j alive)
@@ -978,24 +972,11 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
                 zl[vw][k] = v < V ? z[v] : -INFINITY;
             }
     }
-    const int iter_no = s.cont ? (int)(*(const unsigned*)s.iter_ctr & 0x3fffffffu) : iter_slot;     // same value in every workgroup
-    const int uslot = s.cont ? (iter_no & 63) : iter_slot;                                          // slot of the flag rings
+    const ContSlot rd = cont_round(s, iter_slot, s.done_blocks, true, q == 0 && tid == 0);
+    const int iter_no = rd.no, uslot = rd.slot;
     int* tre = s.trellis + (size_t)(s.cont ? iter_no % s.tring : iter_slot) * s.Md + r0;
-    if (s.cont && q == 0 && tid == 0) {                                                             // recycle the flag rings
-        s.unfinished[(uslot + 32) & 63] = 0;
-        s.done_blocks[(uslot + 32) & 63] = 0;
-    }
-    auto publish = [&]() {           // thread 0 of every workgroup, after its last store of this launch (continuous mode)
-        if (!s.cont) return;
-        if (s.host_flag && !s.lm_on) __threadfence_system();     // this stream's records (pinned memory) before the count
-        if (atomicAdd(&s.done_blocks[uslot], 1) == (int)gridDim.x - 1) {      // last workgroup of the launch
-            if (s.host_flag && !s.lm_on) {
-                const int v = atomicAdd(&s.unfinished[uslot], 0);
-                __hip_atomic_store(s.host_flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            *s.iter_ctr = iter_no + 1;
-        }
-    };
+    // end of the launch (thread 0, after its last store): with an LM attached k_beam_fuse publishes the round, not this kernel
+    auto publish = [&]() { cont_arrive(s, rd, s.done_blocks, true, !s.lm_on); };
     const bool dbg = s.dbg && q == 0 && tid == 0;
     const unsigned long long t_entry = dbg ? wall_clock64() : 0ull;
     const int t = s.t_idx[q], Tr = s.T_row[q];
@@ -1207,21 +1188,6 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     publish();
 }
 
-// continuous beam loop, admission of newly encoded steps (<= 512 streams): frames-available counts by value (as k_ja_admit) and
-// the joint activation of every hypothesis slot of the streams that have a frame to decode (rows = stream * W + slot)
-inline __global__ void k_ja_admit_beam(const float* __restrict__ pe, const float* __restrict__ pp, const int* __restrict__ t_idx,
-                                const AvailV av, int* __restrict__ avail_out, void* __restrict__ ja, int J, int Md, int W, int M_enc,
-                                int MT, int ring, int bf) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= Md * J) return;
-    const int r = idx / J, j = idx - r * J, q = r / W;
-    const int Tav = av.v[q];
-    if (j == 0 && r == q * W) avail_out[q] = Tav;
-    const int t = t_idx[q];
-    if (t >= Tav) return;
-    act_st(bf, ja, act_off(bf, r, j, MT), tanhf(pe[((size_t)(t % ring) * M_enc + q) * J + j] + pp[(size_t)r * J + j]));
-}
-
 // Beam search, one selection round: every hypothesis slot that was NOT extended takes the state of its parent slot (current
 // parity) into its own slot of the other parity -- predictor h / c / BN(h) of every layer, the predictor half of the joint -- and,
 // if its stream still has a frame to decode, its joint activation.  This used to ride in the epilogues of the predictor / joint
@@ -1348,9 +1314,8 @@ __global__ __launch_bounds__(256) void k_beam_fuse(const float* __restrict__ log
                                                    float theta, float lm_min) {
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int W = s.W, V = s.V, q = r / W;
-    const int iter_no = s.cont ? (int)((*(const unsigned*)s.iter_ctr - 1u) & 0x3fffffffu) : iter_slot;   // k_beam_select has moved on by one
-    const int uslot = s.cont ? (iter_no & 63) : iter_slot;
-    if (s.cont && r == 0 && tid == 0) s.done2[(uslot + 32) & 63] = 0;
+    const ContSlot rd = cont_round(s, iter_slot, s.done2, false, r == 0 && tid == 0);     // (k_beam_select_rw's round: it has moved the counter on)
+    const int iter_no = rd.no;
     const int par = s.parent[r], prow = q * W + par;
     if (s.emit[r] && lm_valid[prow]) {               // uniform over the workgroup
         __shared__ float sh4[4];
@@ -1377,62 +1342,14 @@ __global__ __launch_bounds__(256) void k_beam_fuse(const float* __restrict__ log
         if (lane == 0) sh4[w] = part;
         __syncthreads();
         const float lse = logf(sh4[0] + sh4[1] + sh4[2] + sh4[3]);     // (same sums as k_select's: the joint log-softmax the greedy fuser sees)
-        part = 0.f;
-#pragma unroll
-        for (int k = 0; k < KEEP; ++k) {
-            const int j = tid + 256 * k;
-            zv[k] = j < V ? (zv[k] - best) - lse : 0.f;
-            part += zv[k];
-        }
-        const float mean = block_sum_256(part, sh4, lane, w) / (float)V;
-        part = 0.f;
-#pragma unroll
-        for (int k = 0; k < KEEP; ++k) {
-            const int j = tid + 256 * k;
-            zv[k] = j < V ? zv[k] - mean : 0.f;                      // t.add_(-t.mean())
-            part += zv[k];
-        }
-        const float mean2 = block_sum_256(part, sh4, lane, w) / (float)V;   // torch.std subtracts its own mean again
-        part = 0.f;
-#pragma unroll
-        for (int k = 0; k < KEEP; ++k) {
-            const int j = tid + 256 * k;
-            const float d = j < V ? zv[k] - mean2 : 0.f;
-            part += d * d;
-        }
-        const float den = sqrtf(block_sum_256(part, sh4, lane, w) / (float)(V - 1)) + 1e-5f;
-        const float* lz = lmz + (size_t)prow * V;
-        float fb = -INFINITY;
-        int fa = 0x7fffffff;
-#pragma unroll
-        for (int k = 0; k < KEEP; ++k) {
-            const int j = tid + 256 * k;
-            if (j >= V) continue;
-            const float jo = j == 0 ? lm_min : zv[k] / den;
-            const float f = __fadd_rn(__fmul_rn(alpha, lz[j]), __fmul_rn(theta, jo));   // no FMA contraction
-            if (amax_gt(f, fb)) { fb = f; fa = j; }
-        }
-        wave_argmax_f32(fb, fa);
-        __syncthreads();
-        if (lane == 0) { sv[w] = fb; si[w] = fa; }
-        __syncthreads();
-        fb = sv[0]; fa = si[0];
-#pragma unroll
-        for (int k = 1; k < 4; ++k)
-            if (amax_before(sv[k], si[k], fb, fa)) { fb = sv[k]; fa = si[k]; }
-        fa = amax_index(fa, V);
+        const float den = lm_standardise<KEEP>(zv, best, lse, V, sh4, tid);
+        const int fa = lm_fused_argmax<KEEP>(zv, den, lmz + (size_t)prow * V, alpha, theta, lm_min, V, sv, si, tid);
         if (tid == 0) {
             s.token[r] = fa;
             s.trellis[(size_t)(s.cont ? iter_no % s.tring : iter_slot) * s.Md + r] = (par << 16) | (fa + 1);
         }
     }
-    if (tid == 0 && s.cont) {
-        if (s.host_flag) __threadfence_system();
-        if (atomicAdd(&s.done2[uslot], 1) == (int)gridDim.x - 1 && s.host_flag) {
-            const int v = atomicAdd(&s.unfinished[uslot], 0);
-            __hip_atomic_store(s.host_flag, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if (tid == 0) cont_arrive(s, rd, s.done2, false, true);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -154,11 +154,37 @@ inline void launch_logits_from(lasr_ctx* c, const DecView& v, const void* act, i
     else launch_logits_ops<OpsF32>(c, v, act, mtj, row_cap, out, n_rows, false);
 }
 
+// ---------------------------------------------------------------------------- selection family: runtime value -> template argument
+// f(std::integral_constant<int, C>{}) for the first candidate C with v <= C, the last candidate if there is none: the one place
+// a runtime lookahead / slot count / beam width / flag becomes a compile-time constant (f is a generic lambda that names the
+// kernel and writes its argument list once)
+template <int C0, int... Cs, class F>
+inline void with_const(int v, F&& f) {
+    if constexpr (sizeof...(Cs) == 0) f(std::integral_constant<int, C0>{});
+    else if (v <= C0) f(std::integral_constant<int, C0>{});
+    else with_const<Cs...>(v, f);
+}
 // k_lm_post / k_beam_fuse with the register slots their vocabulary needs (bit-identical either way, see k_lm_post)
 inline bool keep16(int V) {
     static const int force = getenv("LASR_KEEP16") ? atoi(getenv("LASR_KEEP16")) : 0;
     return force || V > 2048;
 }
-#define LAUNCH_LM_POST(V_, ...) do { if (keep16(V_)) hipLaunchKernelGGL(k_lm_post<16>, __VA_ARGS__); else hipLaunchKernelGGL(k_lm_post<8>, __VA_ARGS__); } while (0)
-#define LAUNCH_BEAM_FUSE(V_, ...) do { if (keep16(V_)) hipLaunchKernelGGL(k_beam_fuse<16>, __VA_ARGS__); else hipLaunchKernelGGL(k_beam_fuse<8>, __VA_ARGS__); } while (0)
+// k_select with the compile-time lookahead bound that covers `la` (1, 2, 4) and 8 or 16 register slots per thread and frame
+template <bool PLAIN>
+inline void launch_select(hipStream_t st, int rows, const float* logits, int V, int blank, int max_iters, const int* T_row,
+                          const DecState& s, int iter_slot, float* out_logp, int* out_arg, int la, int M) {
+    with_const<8, 16>(V <= 2048 && !s.lmz ? 8 : 16, [&](auto keep) {      // (the LM re-pick keeps the whole row in registers: 16 slots)
+        with_const<1, 2, 4>(la, [&](auto lat) {
+            constexpr int LAT = decltype(lat)::value, KEEP = decltype(keep)::value;
+            hipLaunchKernelGGL((k_select<PLAIN, LAT, KEEP>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters, T_row, s, iter_slot,
+                               out_logp, out_arg, LAT == 1 ? 1 : la, M);
+        });
+    });
+}
+inline void launch_lm_post(hipStream_t st, int rows, const float* raw, const int* emit, float* lmz, int* lm_valid, int V, float min_val,
+                           const int* parent, int W, const float* lmz_in, const int* valid_in) {
+    with_const<8, 16>(keep16(V) ? 16 : 8, [&](auto keep) {
+        hipLaunchKernelGGL(k_lm_post<decltype(keep)::value>, dim3(rows), dim3(256), 0, st, raw, emit, lmz, lm_valid, V, min_val, parent, W, lmz_in, valid_in);
+    });
+}
 

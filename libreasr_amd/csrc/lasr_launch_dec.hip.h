@@ -204,8 +204,8 @@ void launch_lm_t(lasr_ctx* c, DecView& v, bool beam, int l0, int l1, bool tail) 
     EpiLinear::Args ea{};
     ea.bias = m.bout; ea.out = m.raw; ea.ldo = V; ea.n_rows = R; ea.t_idx = nullptr; ea.T_row = nullptr; ea.M = R;
     launch_linear_ops<Ops, true, -1>(c, v, V / 16, R / 16, g, H, ea);
-    LAUNCH_LM_POST(V, dim3(R), dim3(256), 0, v.stream, (const float*)m.raw, (const int*)c->ds.emit, m.lmz[wr], m.valid[wr], V, m.min_val,
-                       beam ? (const int*)c->b_parent : (const int*)nullptr, beam ? c->W : 1, (const float*)m.lmz[rd], (const int*)m.valid[rd]);
+    launch_lm_post(v.stream, R, m.raw, c->ds.emit, m.lmz[wr], m.valid[wr], V, m.min_val, beam ? c->b_parent : nullptr, beam ? c->W : 1,
+                   m.lmz[rd], m.valid[rd]);
     v.lm_par ^= 1;
 }
 // the pair kinds of one operand type (see launch_pair): false = not a kind the templates name

@@ -36,6 +36,5 @@ void launch_lm_q8(lasr_ctx* c, DecView& v) {
     }
     v.lm_par ^= 1;
     lm_q_gemv_pre(c, v, m.qh[m.L - 1], m.sxh[m.L - 1], m.Kp_h, m.qWout, m.s_out, m.bout, m.raw, V, M);
-    LAUNCH_LM_POST(V, dim3(M), dim3(256), 0, v.stream, (const float*)m.raw, (const int*)c->ds.emit, m.lmz[0], m.valid[0], V, m.min_val,
-                       (const int*)nullptr, 1, (const float*)m.lmz[0], (const int*)m.valid[0]);
+    launch_lm_post(v.stream, M, m.raw, c->ds.emit, m.lmz[0], m.valid[0], V, m.min_val, nullptr, 1, m.lmz[0], m.valid[0]);
 }
