@@ -364,6 +364,34 @@ int lasr_align_band_feats(lasr_ctx* c, const int* slots, int n, const float* fea
                           const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
                           int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch);
 
+/* ---- Banded lattice posteriors: lasr_align_band_* plus the backward half of the forward-backward algorithm over the band (DESIGN
+ * 5.7).  With w, valid windows lo, b / e in band layout counting -inf outside the windows, alpha and loglik as lasr_align_band_* has them:
+ *   beta[T-1,U] = b[T-1,U]; beta[t,u] = logaddexp(beta[t+1,u] + b[t,u], beta[t,u+1] + e[t,u]) on window cells; a successor outside ITS
+ *                 frame's window counts -inf: (t+1,u) is inside iff t < T-1 and u >= lo[t+1], (t,u+1) iff u + 1 < lo[t] + w
+ *   occ_blank[t,u] = exp(alpha[t,u] + b[t,u] + beta[t+1,u] - loglik) where (t+1,u) is inside, else 0; occ_blank[T-1,U] = 1
+ *   occ_emit[t,u]  = exp(alpha[t,u] + e[t,u] + beta[t,u+1] - loglik) where (t,u+1) is inside, else 0 (so 0 at k = w-1 and at u = U)
+ * = lasr_align_post_*'s definition on the full [T][U + 1] lattice that holds -inf outside the windows: the probability, over the
+ * alignments that stay inside the windows, that the path takes that edge; sum_t occ_emit[t,u] = 1 (u < U), sum_u occ_blank[t,u] = 1.
+ * Per label u = 1..U, p(t) = occ_emit[t,u-1] over the frames whose window holds column u-1 (0 elsewhere): tok_mean, tok_var,
+ * tok_peak_frame, tok_peak as lasr_align_post_*.  alpha, beta and the occupancies are double on the device; occ_* are rounded once to
+ * f32.  loglik = -inf (windows that leave no path, or an impossible transcript): every occupancy 0, tok_mean -1, tok_var 0,
+ * tok_peak_frame -1, tok_peak 0; never a NaN.  With w == U + 1 every output has lasr_align_post_*'s bits.
+ * Arguments, preconditions, state rules, limits and errors of lasr_align_band_pcm / lasr_align_band_feats, followed by six optional
+ * HOST outputs: occ_blank / occ_emit per utterance [T_i][w_i] f32 in band layout, concatenated (the layout of blank_lp / emit_lp);
+ * tok_mean, tok_var, tok_peak double [sum U_i]; tok_peak_frame int32 [sum U_i].  With max_passes > 1 the posteriors are those of the
+ * last pass's windows (lo_out).  All six null: the call is lasr_align_band_*.  Otherwise alpha and beta occupy 16 bytes per band cell
+ * of workspace: more than 2^24 band cells (sum T_i w_i) in the call is LASR_EINVAL, nothing changed. */
+int lasr_align_band_post_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                             const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                             int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes,
+                             int32_t* touch, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var,
+                             int32_t* tok_peak_frame, double* tok_peak);
+int lasr_align_band_post_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                               const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                               int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes,
+                               int32_t* touch, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var,
+                               int32_t* tok_peak_frame, double* tok_peak);
+
 /* ---- N-best rescoring: one encoder pass per utterance and the lattice over a prefix tree of its candidates.
  * lasr_prefix_tree (host only: no context, no GPU) merges k >= 1 candidates -- tokens: concatenated, n_tokens[j] labels each -- into
  * a tree.  Node 0 is the empty prefix (parent -1, label -1, depth 0); every distinct non-empty prefix is one node; label[v] is the
@@ -438,6 +466,16 @@ int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_l
 int lasr_lattice_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, int n,
                       double* loglik, double* loglik_bwd, float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var,
                       int32_t* tok_peak_frame, double* tok_peak);
+
+/* Banded forward-backward alone (see lasr_align_band_post_*), on n caller-supplied band lattices: inputs and range checks as
+ * lasr_lattice_band_dp, and at most 2^24 band cells in the call (LASR_EINVAL before the windows or a lattice are read).  Results in
+ * HOST memory, filled before the call returns (this one synchronises): loglik [n] (required; the forward sum, bit for bit
+ * lasr_lattice_band_dp's); optional: loglik_bwd [n] = beta[0,0] (loglik up to rounding), occ_blank / occ_emit [cells] f32 in band
+ * layout, tok_mean / tok_var / tok_peak double and tok_peak_frame int32 [sum U_i].  With W == U + 1 the results are
+ * lasr_lattice_post's bit for bit. */
+int lasr_lattice_band_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                           const int32_t* lo, int n, double* loglik, double* loglik_bwd, float* occ_blank, float* occ_emit,
+                           double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak);
 
 /* The tree dynamic programme alone (see lasr_score_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
  * [T_i][N_i] f32, concatenated (emit_lp[t][0] is not read); T, n_nodes [n] and parent [sum N_i] (ids local to the lattice): HOST int32.

@@ -81,6 +81,9 @@ SYMBOLS = [
     ("lasr_align_band_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int] + [_P] * 10),
     ("lasr_align_band_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int] + [_P] * 10),
     ("lasr_lattice_band_dp", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    ("lasr_align_band_post_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int] + [_P] * 16),
+    ("lasr_align_band_post_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int] + [_P] * 16),
+    ("lasr_lattice_band_post", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int] + [_P] * 8),
     ("lasr_prefix_tree", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int)]),
     ("lasr_score_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_score_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -113,14 +113,45 @@ class LibreASR:
         return [int(t) for t in transcript]
 
     def _posteriors(self, r):
-        """per token of an align_pcm(posteriors=True) result: the lattice's view of where the token is, over all alignments.  Both
-        probabilities are float32 values ("peak" is tok_peak rounded as occ_emit was), so posterior <= peak <= 1 holds exactly."""
+        """per token of an align_pcm(posteriors=True) or align_band_post_pcm result: the lattice's view of where the token is, over all
+        alignments (of a band: over those inside its windows; occ_emit is then in band layout, column u - lo[frame]).  Both
+        probabilities are float32 values ("peak" is tok_peak rounded as occ_emit was), so posterior <= peak <= 1 holds exactly.  A
+        token without a best-path frame (-1: no path through the windows) has posterior 0, no times and peak 0."""
         d = self.engine.desc
         dt = d.stride * d.hop / d.sample_rate
-        return [{"posterior": float(r["occ_emit"][int(r["frames"][k]), k]),
-                 "time_mean_s": float(r["tok_mean"][k]) * dt, "time_std_s": float(np.sqrt(r["tok_var"][k])) * dt,
-                 "peak_time_s": float(r["tok_peak_frame"][k]) * dt, "peak": float(np.float32(r["tok_peak"][k]))}
-                for k in range(len(r["frames"]))]
+        lo = r.get("lo")
+        out = []
+        for k in range(len(r["frames"])):
+            f = int(r["frames"][k])
+            if f < 0:
+                out.append({"posterior": 0.0, "time_mean_s": None, "time_std_s": None, "peak_time_s": None, "peak": 0.0})
+                continue
+            out.append({"posterior": float(r["occ_emit"][f, k if lo is None else k - int(lo[f])]),
+                        "time_mean_s": float(r["tok_mean"][k]) * dt, "time_std_s": float(np.sqrt(r["tok_var"][k])) * dt,
+                        "peak_time_s": float(r["tok_peak_frame"][k]) * dt, "peak": float(np.float32(r["tok_peak"][k]))})
+        return out
+
+    def _align_run(self, audio, transcript, call, posteriors, band):
+        """the body of align / align_band: `call(slots, utterances, transcripts)` is the engine call"""
+        many = isinstance(audio, (list, tuple))
+        batch = list(audio) if many else [audio]
+        ys = [self._ids(t) for t in (transcript if many else [transcript])]
+        if len(ys) != len(batch):
+            raise ValueError("one transcript per utterance")
+        slots = [self.engine.open() for _ in batch]
+        try:
+            res = call(slots, [self._utterance(a) for a in batch], ys)
+        finally:
+            for s in slots:
+                self.engine.close_slot(s)
+        out = [{"score": r["loglik"], "viterbi": r["viterbi"], "tokens": self._aligned(y, r["frames"], r["logps"])} for r, y in zip(res, ys)]
+        if posteriors:
+            for o, r in zip(out, res):
+                o["posteriors"] = self._posteriors(r)
+        if band:
+            for o, r in zip(out, res):
+                o["band"] = {"width": int(r["width"]), "passes": int(r["passes"]), "touch": bool(r["touch"])}
+        return out if many else out[0]
 
     def align(self, audio, transcript, posteriors=False, band=None, max_passes=4):
         """Forced alignment of a transcript the caller already has (the teacher-forced RNN-T lattice; greedy engines).  transcript: a
@@ -134,31 +165,27 @@ class LibreASR:
         up to 32767 labels), the windows recentred on the best path for up to max_passes passes; score and viterbi are then those of
         the band (score <= the full lattice's), and "band": {"width": the effective width, "passes": passes run, "touch": whether the
         last pass's path still ran along a window edge -- False is evidence, not proof, that the band did not constrain it} is added.
-        band with posteriors=True raises ValueError (banded posteriors are not built)."""
+        band with posteriors=True raises ValueError: the band's posteriors are align_band's."""
         if band is not None and posteriors:
-            raise ValueError("align: posteriors=True is not available with a band")
-        many = isinstance(audio, (list, tuple))
-        batch = list(audio) if many else [audio]
-        ys = [self._ids(t) for t in (transcript if many else [transcript])]
-        if len(ys) != len(batch):
-            raise ValueError("one transcript per utterance")
-        slots = [self.engine.open() for _ in batch]
-        try:
-            if band is None:
-                res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, posteriors=bool(posteriors))
-            else:
-                res = self.engine.align_pcm(slots, [self._utterance(a) for a in batch], ys, band=int(band), max_passes=int(max_passes))
-        finally:
-            for s in slots:
-                self.engine.close_slot(s)
-        out = [{"score": r["loglik"], "viterbi": r["viterbi"], "tokens": self._aligned(y, r["frames"], r["logps"])} for r, y in zip(res, ys)]
+            raise ValueError("align: posteriors=True with a band is align_band(..., posteriors=True)")
+        if band is None:
+            call = lambda slots, pcm, ys: self.engine.align_pcm(slots, pcm, ys, posteriors=bool(posteriors))
+        else:
+            call = lambda slots, pcm, ys: self.engine.align_pcm(slots, pcm, ys, band=int(band), max_passes=int(max_passes))
+        return self._align_run(audio, transcript, call, posteriors, band is not None)
+
+    def align_band(self, audio, transcript, band=64, max_passes=4, posteriors=True):
+        """align(band=...) for long recordings, with the band's own posteriors: align's dict with "band", and with posteriors=True
+        (lasr_align_band_post_pcm) also "posteriors" as align(posteriors=True) gives them, over the alignments that stay inside the
+        last pass's windows -- where "touch" cannot tell whether the band constrained the path, a token's posterior, time spread and
+        peak are what shows how far its time can be trusted.  A token without a best-path frame (no path through the windows) gets
+        {"posterior": 0.0, "time_mean_s": None, "time_std_s": None, "peak_time_s": None, "peak": 0.0}.  At most 2^24 band cells
+        (frames x width, summed over the call) with posteriors."""
         if posteriors:
-            for o, r in zip(out, res):
-                o["posteriors"] = self._posteriors(r)
-        if band is not None:
-            for o, r in zip(out, res):
-                o["band"] = {"width": int(r["width"]), "passes": int(r["passes"]), "touch": bool(r["touch"])}
-        return out if many else out[0]
+            call = lambda slots, pcm, ys: self.engine.align_band_post_pcm(slots, pcm, ys, int(band), max_passes=int(max_passes))
+        else:
+            call = lambda slots, pcm, ys: self.engine.align_pcm(slots, pcm, ys, band=int(band), max_passes=int(max_passes))
+        return self._align_run(audio, transcript, call, posteriors, True)
 
     def score(self, audio, candidates):
         """log P(candidate | audio), summed over all alignments, of every candidate transcript of ONE utterance (rescoring an n-best

@@ -1768,16 +1768,16 @@ int lasr_transcribe_feats(lasr_ctx* c, const int* slots, int n, const float* fea
 }
 
 // ---------------------------------------------------------------------------- teacher-forced lattice
-// The banded lattice is compiled at the END of this unit -- lasr_lattice_band.hip.h and its entry points follow the
-// last function below -- and align_impl reaches it through these declarations.
+// The banded lattice is compiled at the END of this unit -- lasr_lattice_band.hip.h, lasr_lattice_band_post.hip.h
+// and their entry points follow the last function below -- and align_impl reaches it through these declarations.
 namespace lasr {
 constexpr int LAT_BAND_WMAX = 1536;    // window width: four diagonals of doubles (48 KB) + 16 KB of back-pointers = 64 KB of LDS
 constexpr int LAT_BAND_UMAX = 32767;   // labels per transcript of a banded call (the teacher-forced predictor keeps (U + 1) rows x J)
 }
 namespace {
 struct LatBandIO;
-int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io);
-int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io);
+int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io, bool post);
+int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io, const LatPostOut* post);
 }
 // a posterior call keeps alpha and beta of every cell: refused beyond LAT_POST_CELLS, before anything is read or changed
 static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) {
@@ -1786,7 +1786,8 @@ static int post_check_cells(lasr_ctx* c, const int* T, const int32_t* U, int n) 
     if (cells > LAT_POST_CELLS) return fail(c, LASR_EINVAL, "posteriors of a lattice of %lld cells (at most %lld)", cells, LAT_POST_CELLS);
     return LASR_OK;
 }
-// lasr_align_*.  post: the posterior outputs of lasr_align_post_* (null: none); band: lasr_align_band_* (null: the full lattice).
+// lasr_align_*.  post: the posterior outputs of lasr_align_post_* / lasr_align_band_post_* (null: none); band: lasr_align_band_* (null:
+// the full lattice).  The cell limit of a posterior call counts the cells it keeps: the full lattice's here, a band's in lat_band_plan.
 // A greedy, idle context, open slots, a valid transcript per utterance, and the refusals that need the frame counts: nothing has
 // changed when it fails before the front half
 struct AlignCall { const int* slots; int n; const int32_t* tokens; const int32_t* n_tokens; LatOut o; const LatPostOut* post; const LatBandIO* band; };
@@ -1802,10 +1803,10 @@ static int align_impl(lasr_ctx* c, const AlignCall& a, const OfflineAudio& au) {
     HIPCHK(c, hipSetDevice(c->device));
     OfflineDims D;
     RC(offline_dims(c, a.n, au, D));
-    if (a.post) RC(post_check_cells(c, D.Tp.data(), a.n_tokens, a.n));
-    if (a.band) RC(lat_band_plan(c, D.Tp.data(), a.n_tokens, a.n, *a.band));
+    if (a.post && !a.band) RC(post_check_cells(c, D.Tp.data(), a.n_tokens, a.n));
+    if (a.band) RC(lat_band_plan(c, D.Tp.data(), a.n_tokens, a.n, *a.band, a.post != nullptr));
     RC(offline_front(c, au, D, OfflineRows{a.slots, a.n, a.slots, a.n, true}));
-    if (a.band) return lat_finish_band(c, a.slots, a.n, a.tokens, a.o, *a.band);
+    if (a.band) return lat_finish_band(c, a.slots, a.n, a.tokens, a.o, *a.band, a.post);
     return lat_finish(c, a.slots, a.n, D.Tp.data(), a.tokens, a.n_tokens, a.o, a.post);
 }
 int lasr_align_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
@@ -2984,7 +2985,7 @@ int lasr_debug_config(lasr_ctx* c, const char* key, int* value) {
         {"lat_R", LAT_R}, {"lat_umax", LAT_UMAX},      // lattice (lasr_align_*): rows per block, labels per transcript; with profiling on,
         {"lat_enc_us", c->lat.us[0]}, {"lat_pred_us", c->lat.us[1]}, {"lat_blocks_us", c->lat.us[2]}, {"lat_dp_us", c->lat.us[3]},   // the last call's stages
         {"lat_band_wmax", LAT_BAND_WMAX}, {"lat_band_umax", LAT_BAND_UMAX}, {"lat_bp_words", LAT_BP_WORDS},   // banded lattice (lasr_align_band_*): widest window, labels per transcript; back-pointer words a workgroup keeps in LDS
-        {"lat_post_us", c->lat.us[4]},                 // (alpha / beta and occupancies of the last lasr_align_* / lasr_align_post_* / lasr_score_* call: 0 unless it asked for posteriors; the lasr_lattice_* hooks record no stage times)
+        {"lat_post_us", c->lat.us[4]},                 // (alpha / beta and occupancies of the last lasr_align_* / lasr_align_post_* / lasr_align_band_post_* / lasr_score_* call: 0 unless it asked for posteriors; the lasr_lattice_* hooks record no stage times)
     };
     for (const auto& e : tab)
         if (!strcmp(e.k, key)) { *value = e.v; return LASR_OK; }
@@ -3029,9 +3030,10 @@ int lasr_bench_cell(lasr_ctx* c, int layer, int iters, double* us) {
 
 #include "lasr_front.hip.h"
 
-// ---------------------------------------------------------------------------- banded lattice
+// ---------------------------------------------------------------------------- banded lattice and its posteriors (5.7)
 #include "lasr_band_windows.hip.h"
 #include "lasr_lattice_band.hip.h"
+#include "lasr_lattice_band_post.hip.h"
 extern "C" {
 // lasr_align_* over a band of `band` labels per frame
 int lasr_band_windows(int T, int U, int band, const int32_t* frames, const int32_t* lo_cur, int32_t* lo_out, int* touch) {
@@ -3053,14 +3055,33 @@ int lasr_align_band_feats(lasr_ctx* c, const int* slots, int n, const float* fea
     const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, nullptr, &io};
     return align_impl(c, a, OfflineAudio{feats, nullptr, n_frames});
 }
-
-// the banded programme: W and lo [sum T] beside T and U
-int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
-                         const int32_t* lo, int n, double* loglik, double* viterbi, int32_t* frames) {
-    if (!c) return LASR_EINVAL;
-    if (!blank_lp || !emit_lp || !T || !U || !W || !lo || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
+// lasr_align_band_* with the band's edge posteriors; all six posterior outputs null: lasr_align_band_* itself
+int lasr_align_band_post_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const int64_t* n_samples, const int32_t* tokens,
+                             const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                             int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch,
+                             float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
     LatCall k;
-    TabImage img;
+    const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
+    const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, lat_post_any(p) ? &p : nullptr, &io};
+    return align_impl(c, a, OfflineAudio{pcm, n_samples, nullptr});
+}
+int lasr_align_band_post_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* tokens,
+                               const int32_t* n_tokens, int band, int max_passes, const int32_t* lo_in, double* loglik, double* viterbi,
+                               int32_t* frames, float* logps, float* blank_lp, float* emit_lp, int32_t* lo_out, int32_t* passes, int32_t* touch,
+                               float* occ_blank, float* occ_emit, double* tok_mean, double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
+    LatCall k;
+    const LatBandIO io{band, max_passes, lo_in, lo_out, passes, touch, &k};
+    const LatPostOut p{nullptr, nullptr, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    const AlignCall a{slots, n, tokens, n_tokens, LatOut{loglik, viterbi, frames, logps, blank_lp, emit_lp}, lat_post_any(p) ? &p : nullptr, &io};
+    return align_impl(c, a, OfflineAudio{feats, nullptr, n_frames});
+}
+
+// head of lasr_lattice_band_dp / lasr_lattice_band_post: the arguments, the call description with W and lo [sum T] beside T and U, and
+// its tables on the device.  post: the cell limit of a posterior call, before the windows or a lattice are read
+static int lattice_band_call(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                             const int32_t* lo, int n, const double* loglik, bool post, LatCall& k, TabImage& img) {
+    if (!blank_lp || !emit_lp || !T || !U || !W || !lo || !loglik || n < 1) return fail(c, LASR_EINVAL, "bad argument");
     k.n = n;
     k.T.assign(T, T + n); k.U.assign(U, U + n); k.W.assign(W, W + n); k.slot.assign(n, 0);
     for (int i = 0; i < n; ++i)
@@ -3068,15 +3089,36 @@ int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_l
             return fail(c, LASR_EINVAL, "lattice %d: T = %d, U = %d, W = %d (T >= 1, 0 <= U <= %d, 1 <= W <= min(U + 1, %d), W = U + 1 where T = 1)",
                         i, T[i], U[i], W[i], LAT_BAND_UMAX, LAT_BAND_WMAX);
     RC(lat_layout_checked(c, k));
+    if (post) RC(lat_band_post_cells(c, k));
     k.lo.assign(lo, lo + k.sumT);
     for (int i = 0; i < n; ++i)
         if (!lasr_bw::valid(T[i], U[i], W[i], lo + k.lo_off[i])) return fail(c, LASR_EINVAL, "lattice %d: lo is not a valid set of windows of width %d", i, W[i]);
     HIPCHK(c, hipSetDevice(c->device));
     lat_pack(k, nullptr, img);
-    RC(lat_upload(c, c->lat, img));
+    return lat_upload(c, c->lat, img);
+}
+// the banded programme
+int lasr_lattice_band_dp(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                         const int32_t* lo, int n, double* loglik, double* viterbi, int32_t* frames) {
+    if (!c) return LASR_EINVAL;
+    LatCall k;
+    TabImage img;
+    RC(lattice_band_call(c, blank_lp, emit_lp, T, U, W, lo, n, loglik, false, k, img));
     RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) {
         return lat_band_run_dp(c, c->lat, k, b, e, viterbi || frames, frames != nullptr, false);
     }));
     return lat_copy_out(c, c->lat, k, LatOut{loglik, viterbi, frames, nullptr, nullptr, nullptr});
+}
+// the banded forward-backward programme
+int lasr_lattice_band_post(lasr_ctx* c, const float* blank_lp, const float* emit_lp, const int32_t* T, const int32_t* U, const int32_t* W,
+                           const int32_t* lo, int n, double* loglik, double* loglik_bwd, float* occ_blank, float* occ_emit, double* tok_mean,
+                           double* tok_var, int32_t* tok_peak_frame, double* tok_peak) {
+    if (!c) return LASR_EINVAL;
+    LatCall k;
+    TabImage img;
+    RC(lattice_band_call(c, blank_lp, emit_lp, T, U, W, lo, n, loglik, true, k, img));
+    const LatPostOut p{loglik, loglik_bwd, occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak};
+    RC(lattice_hook(c, blank_lp, emit_lp, k.cells, [&](const float* b, const float* e) { return lat_band_post_launch(c, c->lat, k, b, e, p); }));
+    return lat_post_copy(c, c->lat, k, p);
 }
 }  // extern "C"

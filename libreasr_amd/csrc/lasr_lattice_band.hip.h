@@ -9,7 +9,8 @@
 //   LatBandMap      (lasr_lattice.hip.h) that layout for k_lat_ja / k_lat_pick: the same LAT_R blocks, logits GEMM, lat_row_lse and
 //                   label tail, so from the same logits a term has the bits lasr_align_* gives the same cell
 //   k_lat_dp_band   both recursions of one utterance per workgroup over anti-diagonals, LDS indexed by t mod w
-// The call description, its layout and its tables are lasr_lattice_tables.hip.h's LatCall with W and lo set.
+// The call description, its layout and its tables are lasr_lattice_tables.hip.h's LatCall with W and lo set.  The band's posteriors
+// (lasr_align_band_post_*) are lasr_lattice_band_post.hip.h, included behind this header; lat_finish_band launches them.
 #pragma once
 
 namespace lasr {
@@ -145,8 +146,16 @@ int lat_band_run_dp(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const f
 // the banded inputs and outputs of lasr_align_band_* beside lasr_align_*'s
 struct LatBandIO { int band, max_passes; const int32_t* lo_in; int32_t* lo_out; int32_t* passes; int32_t* touch; LatCall* plan; };
 
-// widths and first windows of a lasr_align_band_* call from its frame counts (host only; nothing has changed when it fails)
-int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io) {
+// a banded posterior call keeps alpha and beta of every BAND cell (lasr_lattice_band_post.hip.h): refused beyond LAT_POST_CELLS
+int lat_band_post_cells(lasr_ctx* c, const LatCall& k) {
+    if (k.cells > LAT_POST_CELLS) return fail(c, LASR_EINVAL, "posteriors of a band lattice of %lld cells (at most %lld)", k.cells, LAT_POST_CELLS);
+    return LASR_OK;
+}
+int lat_band_post_launch(lasr_ctx* c, lasr_ctx::Lattice& w, const LatCall& k, const float* b, const float* e, const LatPostOut& p);
+
+// widths and first windows of a lasr_align_band_* call from its frame counts (host only; nothing has changed when it fails).
+// post: a lasr_align_band_post_* call that asks for posteriors
+int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatBandIO& io, bool post) {
     LatCall& k = *io.plan;
     if (io.band < 1 || io.max_passes < 1) return fail(c, LASR_EINVAL, "band = %d, max_passes = %d (both >= 1)", io.band, io.max_passes);
     k.n = n;
@@ -157,6 +166,7 @@ int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatB
             return fail(c, LASR_EINVAL, "utterance %d: a window of %d labels (at most %d; a single frame needs U + 1)", i, k.W[i], LAT_BAND_WMAX);
     }
     RC(lat_layout_checked(c, k));
+    if (post) RC(lat_band_post_cells(c, k));
     k.lo.resize((size_t)k.sumT);
     for (int i = 0; i < n; ++i) {
         int32_t* lo = k.lo.data() + k.lo_off[i];
@@ -170,7 +180,8 @@ int lat_band_plan(lasr_ctx* c, const int* T, const int32_t* U, int n, const LatB
 // lat_finish over a band (io.plan: lat_band_plan's, slots not yet set): the teacher-forced predictor once, then per pass the band cells of
 // every utterance through the joint and the banded dynamic programme; between passes the best paths come to the host and
 // lasr_band_windows' routine recentres the windows.  The loop ends when no utterance touches, no window changed, or at max_passes.
-int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io) {
+// post (lasr_align_band_post_*): alpha / beta and the occupancies behind the loop, on the last pass's b / e, windows and tables.
+int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const LatOut& o, const LatBandIO& io, const LatPostOut* post) {
     LatCall& k = *io.plan;
     lasr_ctx::Lattice& w = c->lat;
     k.slot.assign(slots, slots + n);
@@ -213,8 +224,14 @@ int lat_finish_band(lasr_ctx* c, const int* slots, int n, const int32_t* tokens,
         if (!any_touch || !changed || passes >= io.max_passes) break;
         k.lo.swap(lo_new);
     }
+    if (post) {                                       // (k.lo and k.tab are the last pass's; loglik stays the dynamic programme's)
+        RC(lat_band_post_launch(c, w, k, w.b, w.e, *post));
+        lat_mark(c, w, 5);
+        w.ev_post = c->profiling && w.ev_ok;
+    }
     RC(lat_release(c, slots, n));
     RC(lat_copy_out(c, w, k, o));
+    if (post) RC(lat_post_copy(c, w, k, *post));
     if (io.lo_out) memcpy(io.lo_out, k.lo.data(), sizeof(int32_t) * (size_t)k.sumT);
     for (int i = 0; i < n; ++i) {
         if (io.passes) io.passes[i] = passes;

@@ -379,7 +379,7 @@ class Engine:
     def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi, posteriors=False, band=None, max_passes=1, windows=None):
         if band is not None:
             if posteriors:
-                raise ValueError("posteriors are not available with a band")
+                raise ValueError("posteriors with a band: use align_band_post_pcm / align_band_post_feats")
             return self._align_band(fn is self.lib.lasr_align_pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows)
         a, p, n = self._slots(slots)
         assert len(token_lists) == n
@@ -421,8 +421,9 @@ class Engine:
             out.append(r)
         return out
 
-    def _align_band(self, pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows):
-        """lasr_align_band_pcm / _feats: _align's dicts with the lattice arrays [T, w] in band layout, and "lo", "width", "passes", "touch"."""
+    def _align_band(self, pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=False):
+        """lasr_align_band_pcm / _feats: _align's dicts with the lattice arrays [T, w] in band layout, and "lo", "width", "passes", "touch";
+        posteriors (lasr_align_band_post_pcm / _feats): also lattice_post's six fields, the occupancies [T, w] in band layout."""
         a, p, n = self._slots(slots)
         assert len(token_lists) == n
         toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
@@ -446,9 +447,14 @@ class Engine:
         lo = np.zeros(max(int(sum(Ts)), 1), dtype=np.int32)
         passes, touch = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
         fn = self.lib.lasr_align_band_pcm if pcm else self.lib.lasr_align_band_feats
-        self._chk(fn(self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p), U.ctypes.data_as(C.c_void_p),
-                     int(band), int(max_passes), _ptr(lo_in), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e), _ptr(lo),
-                     _ptr(passes), _ptr(touch)))
+        args = (self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p), U.ctypes.data_as(C.c_void_p),
+                int(band), int(max_passes), _ptr(lo_in), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e), _ptr(lo),
+                _ptr(passes), _ptr(touch))
+        if posteriors:
+            post = self._post_buffers(max(cells, 1), int(tok.size))
+            fn = self.lib.lasr_align_band_post_pcm if pcm else self.lib.lasr_align_band_post_feats
+            args += tuple(_ptr(x) for x in post)
+        self._chk(fn(*args))
         out, o, oc, ot = [], 0, 0, 0
         for i in range(n):
             u, t, w = int(U[i]), int(Ts[i]), W[i]
@@ -458,6 +464,8 @@ class Engine:
             if lattice:
                 r.update(blank_lp=b[oc:oc + t * w].reshape(t, w).copy(), emit_lp=e[oc:oc + t * w].reshape(t, w).copy())
             r.update(lo=lo[ot:ot + t].copy(), width=w, passes=int(passes[i]), touch=int(touch[i]))
+            if posteriors:
+                r.update(self._post_slice(post, t, u, oc, o, w))
             o += u
             oc += t * w
             ot += t
@@ -489,18 +497,7 @@ class Engine:
         """The banded dynamic programme alone (lasr_lattice_band_dp) on caller-supplied band lattices: blank / emit = lists of
         [T_i, w_i] float32 arrays in band layout (row t holds the columns lo_i[t] .. lo_i[t] + w_i - 1), lo = their window starts,
         U = their label counts.  -> per lattice {"loglik", "viterbi", "frames"}."""
-        n = len(blank)
-        assert n == len(emit) == len(lo) == len(U) and n >= 1
-        bs = [np.asarray(x, dtype=np.float32) for x in blank]
-        es = [np.asarray(x, dtype=np.float32) for x in emit]
-        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
-        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
-        W = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
-        Us = np.ascontiguousarray(np.array([int(u) for u in U], dtype=np.int32))
-        los = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in lo]))
-        assert los.size == int(T.sum())
-        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
-        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        n, b, e, T, Us, W, los = self._band_lattices(blank, emit, lo, U)
         loglik = np.zeros(n, dtype=np.float64)
         vit = np.zeros(n, dtype=np.float64) if viterbi else None
         fr = np.zeros(max(int(Us.sum()), 1), dtype=np.int32) if viterbi else None
@@ -516,6 +513,41 @@ class Engine:
         return out
 
     @staticmethod
+    def _band_lattices(blank, emit, lo, U):
+        """the inputs of lattice_band_dp / lattice_band_post concatenated -> (n, b, e, T, U, W, lo)"""
+        n = len(blank)
+        assert n == len(emit) == len(lo) == len(U) and n >= 1
+        bs = [np.asarray(x, dtype=np.float32) for x in blank]
+        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
+        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
+        W = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
+        Us = np.ascontiguousarray(np.array([int(u) for u in U], dtype=np.int32))
+        los = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in lo]))
+        assert los.size == int(T.sum())
+        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
+        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
+        return n, b, e, T, Us, W, los
+
+    def lattice_band_post(self, blank, emit, lo, U):
+        """Banded forward-backward alone (lasr_lattice_band_post) on caller-supplied band lattices, the arguments of lattice_band_dp.
+        -> per lattice lattice_post's dict, "occ_blank" / "occ_emit" [T, w] float32 in band layout."""
+        n, b, e, T, Us, W, los = self._band_lattices(blank, emit, lo, U)
+        loglik, bwd = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        post = self._post_buffers(int(b.size), int(Us.sum()))
+        self._chk(self.lib.lasr_lattice_band_post(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Us), _ptr(W), _ptr(los), n, _ptr(loglik), _ptr(bwd),
+                                                  *[_ptr(x) for x in post]))
+        out, o, oc = [], 0, 0
+        for i in range(n):
+            t, u, w = int(T[i]), int(Us[i]), int(W[i])
+            r = {"loglik": float(loglik[i]), "loglik_bwd": float(bwd[i])}
+            r.update(self._post_slice(post, t, u, oc, o, w))
+            o += u
+            oc += t * w
+            out.append(r)
+        return out
+
+    @staticmethod
     def _post_buffers(cells, n_tok):
         """host outputs of a posterior call, in the order of the C arguments: occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak"""
         k = max(n_tok, 1)
@@ -523,9 +555,11 @@ class Engine:
                 np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64))
 
     @staticmethod
-    def _post_slice(post, t, u, oc, o):
+    def _post_slice(post, t, u, oc, o, row=None):
+        """one utterance of the posterior outputs: t rows of `row` cells from oc (None: the full lattice's u + 1), u labels from o"""
         ob, oe, mean, var, pf, peak = post
-        return dict(occ_blank=ob[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(), occ_emit=oe[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(),
+        row = u + 1 if row is None else row
+        return dict(occ_blank=ob[oc:oc + t * row].reshape(t, row).copy(), occ_emit=oe[oc:oc + t * row].reshape(t, row).copy(),
                     tok_mean=mean[o:o + u].copy(), tok_var=var[o:o + u].copy(), tok_peak_frame=pf[o:o + u].copy(), tok_peak=peak[o:o + u].copy())
 
     def _align_frames(self, lens, pcm):
@@ -545,7 +579,13 @@ class Engine:
         band=W (lasr_align_band_pcm): the lattice restricted to W labels per frame -- w = min(W, U + 1) (U + 1 on a single frame) --
         starting from `windows` (per utterance the T window starts; None: linear) and recentred on the best path for up to max_passes
         passes; transcripts of up to 32767 labels.  The dict then also has "lo" int32 [T] (the last pass's windows), "width",
-        "passes" and "touch", and the lattice arrays are [T, w] in band layout (row t holds the columns lo[t] .. lo[t] + w - 1)."""
+        "passes" and "touch", and the lattice arrays are [T, w] in band layout (row t holds the columns lo[t] .. lo[t] + w - 1).
+        band with posteriors=True raises ValueError: the band's posteriors are align_band_post_pcm's."""
+        cat, ns = self._align_pcm_input(slots, pcm_list)
+        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
+
+    def _align_pcm_input(self, slots, pcm_list):
+        """the utterances of an align_*_pcm call concatenated (host, or device when all of them are) and their sample counts"""
         a, p, n = self._slots(slots)
         assert len(pcm_list) == n
         if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
@@ -554,11 +594,15 @@ class Engine:
             cat = np.ascontiguousarray(np.concatenate([
                 np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
                 for x in pcm_list]))
-        ns = np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
-        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
+        return cat, np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
 
     def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True, posteriors=False, band=None, max_passes=1, windows=None):
         """align_pcm from stacked features (lasr_align_feats; with a band lasr_align_band_feats): feats_list as for transcribe_feats."""
+        cat, nf = self._align_feats_input(slots, feats_list)
+        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
+
+    def _align_feats_input(self, slots, feats_list):
+        """the stacked features of an align_*_feats call concatenated (host, or device when all of them are) and their frame counts"""
         a, p, n = self._slots(slots)
         assert len(feats_list) == n
         F = self.desc.feat
@@ -569,8 +613,22 @@ class Engine:
             arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
             cat = np.ascontiguousarray(np.concatenate(arrs))
             nf = [a_.shape[0] for a_ in arrs]
-        nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
-        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
+        return cat, np.ascontiguousarray(np.array(nf, dtype=np.int32))
+
+    def align_band_post_pcm(self, slots, pcm_list, token_lists, band, max_passes=1, windows=None, lattice=False, viterbi=True):
+        """align_pcm(band=...) with the BAND's edge posteriors (lasr_align_band_post_pcm): the dicts of the banded call -- "lo", "width",
+        "passes", "touch", lattice arrays [T, w] in band layout -- plus "occ_blank" / "occ_emit" [T, w] float32 in band layout
+        (occ_emit[t, k] = the probability, over the alignments inside the windows, that label lo[t] + k + 1 is emitted on frame t) and
+        per label "tok_mean", "tok_var", "tok_peak_frame", "tok_peak" as align_pcm(posteriors=True).  With max_passes > 1 they are
+        those of the last pass's windows ("lo").  No path through the windows (loglik -inf): occupancies 0, tok_mean -1, tok_var 0,
+        tok_peak_frame -1, tok_peak 0.  At most 2^24 band cells in the call."""
+        cat, ns = self._align_pcm_input(slots, pcm_list)
+        return self._align_band(True, slots, cat, ns, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=True)
+
+    def align_band_post_feats(self, slots, feats_list, token_lists, band, max_passes=1, windows=None, lattice=False, viterbi=True):
+        """align_band_post_pcm from stacked features (lasr_align_band_post_feats): feats_list as for transcribe_feats."""
+        cat, nf = self._align_feats_input(slots, feats_list)
+        return self._align_band(False, slots, cat, nf, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=True)
 
     def lattice_dp(self, blank, emit, viterbi=True):
         """The lattice dynamic programme alone (lasr_lattice_dp) on caller-supplied lattices: blank / emit = lists of [T_i, U_i + 1]

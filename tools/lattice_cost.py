@@ -12,6 +12,8 @@ Banded leg: the utterance tiled 4x (82.6 s) with the engine's own g
 lasr_align_pcm on the full lattice beside lasr_align_band_pcm with band = 64 at max_passes 1 and 4 -- stage times (with several
 passes blocks_ms runs from the end of the predictor to the end of the last pass's blocks, dp_ms is the last pass's), cells, passes,
 touch, and how far the banded viterbi score and frames are from the full lattice's.
+Banded posterior leg: each banded call again through lasr_align_band_post_pcm, beside the plain banded leg of the same
+process: post_ms is the added stage (alpha / beta and the occupancies over the last pass's band), to be set against dp_ms.
     python tools/lattice_cost.py [f32|bf16]"""
 import json
 import os
@@ -102,5 +104,13 @@ if hasattr(eng, "lattice_band_dp"):
             leg.update(viterbi_minus_full=r["viterbi"] - full["viterbi"], loglik_minus_full=r["loglik"] - full["loglik"],
                        frames_differ=int((d > 0).sum()), frames_max_abs_diff=int(d.max()) if d.size else 0)
         out[f"long_band64_p{mp}"] = leg
+        if hasattr(eng, "align_band_post_pcm"):
+            leg, res, st = timed(lambda: eng.align_band_post_pcm(slots[:1], [long_pcm], [yl], 64, max_passes=mp))
+            p = res[0]
+            leg.update(cells=Tl * p["width"], passes=p["passes"], post_over_dp=round(st[4] / st[3], 3) if st[3] else None, loglik=p["loglik"],
+                       same_path=bool(np.array_equal(p["frames"], r["frames"]) and p["loglik"] == r["loglik"]),
+                       mean_time_std_frames=round(float(np.sqrt(p["tok_var"]).mean()), 4) if len(yl) else None,
+                       min_path_posterior=float(min(p["occ_emit"][int(t), u - int(p["lo"][int(t)])] for u, t in enumerate(p["frames"]))) if len(yl) else None)
+            out[f"long_band64_p{mp}_post"] = leg
 eng.close()
 print(json.dumps(out))
