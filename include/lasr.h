@@ -426,6 +426,27 @@ int lasr_score_pcm(lasr_ctx* c, const int* slots, int n, const float* pcm, const
 int lasr_score_feats(lasr_ctx* c, const int* slots, int n, const float* feats, const int32_t* n_frames, const int32_t* n_cands,
                      const int32_t* tokens, const int32_t* n_tokens, double* loglik, double* viterbi, float* blank_lp, float* emit_lp);
 
+/* ---- LM sequence scoring: log P_LM of n candidate transcripts by the attached LM (the second term of the usual second-pass
+ * combination log P_rnnt(y | x) + lambda log P_LM(y) + gamma |y|; lasr_score_* gives the first).
+ * Replaces: LM.forward on a whole sequence (lm.py:31-40) followed by the gather of the target labels' entries.
+ * Candidate i is y_1..y_U, U = n_tokens[i]; tokens: the candidates concatenated (HOST).
+ *   start >= 0:  the LM reads x = (start, y_1, .., y_{U-1}) from zero state; lp[u-1] = log_softmax(LM(x_1..x_u))[y_u], u = 1..U.
+ *   start == -1: the LM reads y_1..y_{U-1}; lp[0] = 0 (no term: the reference's fuser has no LM distribution before the first emitted
+ *                token, lm.py:46,58); lp[u-1] = log_softmax(LM(y_1..y_{u-1}))[y_u], u = 2..U.
+ * total[i] = the sum of the f32 terms lp[0..U) in label order, accumulated in double on the device; U = 0 gives 0.  A term is
+ * (z[y] - m) - lse with the maximum and the exp-sum taken as for the lattice's terms (lasr_align_*).  Operand type, rounding points and
+ * accumulation are the attached LM's: f32, the context's bf16 operands, or the int8-served form (lasr_attach_lm_int8).
+ * Every candidate occupies one open, distinct slot -- its LM row -- so n <= max_streams.  Outputs, HOST memory, filled before the call
+ * returns: total [n] (required), logps [sum U_i] (optional).
+ * LASR_ESTATE: no LM attached; a submitted step is uncollected.  The listed slots' LM state is reset at the start and at the end: they
+ * are left as lasr_stream_reset(slot, 4) leaves them.  Nothing else changes: their encoder, predictor, front-end and uncollected results
+ * stay, and so does every other slot's state, its LM state included.
+ * LASR_EINVAL, nothing changed: a label out of [0, vocab) or equal to blank; start < -1 or start >= vocab (start may be any id, blank
+ * included); n_tokens[i] < 0 or > 1535; n < 1 or n > max_streams; a slot listed twice or not open; a null required argument; beam > 1
+ * (the LM rows of a beam context are hypothesis slots behind a parent indirection; the same follow-up as the lattice calls'). */
+int lasr_lm_score(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const int32_t* n_tokens, int start, double* total,
+                  float* logps);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */

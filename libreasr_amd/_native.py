@@ -88,6 +88,7 @@ SYMBOLS = [
     ("lasr_score_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_score_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_lattice_tree_dp", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
+    ("lasr_lm_score", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
     ("lasr_logmel", C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     ("lasr_stack", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     ("lasr_encoder", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

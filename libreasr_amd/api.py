@@ -225,6 +225,44 @@ class LibreASR:
                 vit += [float(v) for v in r["viterbi"]]
         return (out, vit) if viterbi else out
 
+    def lm_score(self, candidates, start=None):
+        """log P_LM(candidate) by the attached LM, of every candidate transcript (text or ids, as in `score`), in the candidates'
+        order: one engine call per group of up to max_streams candidates.  start=None: the LM reads the labels themselves and the
+        first one has no term; start=id: the LM reads that token first and every label has a term."""
+        ys = [self._ids(t) for t in candidates]
+        out, g = [], self.engine.max_streams
+        for i in range(0, len(ys), g):
+            part = ys[i:i + g]
+            slots = [self.engine.open() for _ in part]
+            try:
+                out += [float(r["total"]) for r in self.engine.lm_score(slots, part, start=start)]
+            finally:
+                for s in slots:
+                    self.engine.close_slot(s)
+        return out
+
+    def rescore_lm(self, audio, candidates, lm_weight, length_bonus=0.0, start=None):
+        """Second-pass combination of ONE utterance's candidates: score = log P(candidate | audio) + lm_weight * log P_LM(candidate)
+        + length_bonus * |candidate|, in float64.  Per group of up to max_streams candidates the slots are opened once and serve
+        `rescore`'s engine call and `lm_score`'s.  -> {"am": rescore's scores, "lm": lm_score's totals, "score": the combination,
+        "best": index of the largest score (a tie takes the lowest index), "order": indices by score descending, ties by index}."""
+        ys = [self._ids(t) for t in candidates]
+        pcm = self._utterance(audio)
+        am, lm, g = [], [], self.engine.max_streams
+        for i in range(0, len(ys), g):
+            part = ys[i:i + g]
+            slots = [self.engine.open() for _ in part]
+            try:
+                am += [float(v) for v in self.engine.score_pcm([slots], [pcm], [part])[0]["loglik"]]
+                lm += [float(r["total"]) for r in self.engine.lm_score(slots, part, start=start)]
+            finally:
+                for s in slots:
+                    self.engine.close_slot(s)
+        score = [float(np.float64(a) + np.float64(lm_weight) * np.float64(l) + np.float64(length_bonus) * np.float64(len(y)))
+                 for a, l, y in zip(am, lm, ys)]
+        order = sorted(range(len(score)), key=lambda j: (-score[j], j))
+        return {"am": am, "lm": lm, "score": score, "best": order[0] if order else None, "order": order}
+
     def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the
         hypothesis so far after every model call.

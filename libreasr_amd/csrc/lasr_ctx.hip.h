@@ -357,6 +357,15 @@ struct lasr_ctx {
         int us[5] = {0, 0, 0, 0, 0};  // lasr_set_profiling: front-end + encoder, predictor, lattice blocks, DP, posteriors of the last call (us)
     } lat;
 
+    // LM sequence scoring (lasr_lm_score, lasr_lm_score.hip.h): workspaces, all null until the first such call; they grow through
+    // ensure_buf
+    struct LmScore {
+        int* tab = nullptr; size_t tab_n = 0;             // per-call tables: [n] row, [n] first term, [n][passes] target label
+        float* lp = nullptr; size_t lp_n = 0;             // [sum U] the terms
+        double* acc = nullptr; size_t acc_n = 0;          // [n] their sums
+        std::vector<int> host;                            // host image of tab (alive until the stream has passed its copy)
+    } lms;
+
     // stats
     bool profiling = false;
     hipEvent_t ev[8];

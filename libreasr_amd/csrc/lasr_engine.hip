@@ -23,6 +23,7 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_lattice_post.hip.h"
 #include "lasr_prefix_tree.hip.h"
 #include "lasr_lattice_tree.hip.h"
+#include "lasr_lm_score.hip.h"
 #include "lasr_weights.hip.h"
 
 
@@ -1983,6 +1984,30 @@ int lasr_lattice_tree_dp(lasr_ctx* c, const float* blank_lp, const float* emit_l
     HIPCHK(c, hipMemcpy(loglik, w.res, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
     if (viterbi) HIPCHK(c, hipMemcpy(viterbi, w.res + k.nodes, sizeof(double) * (size_t)k.nodes, hipMemcpyDeviceToHost));
     return LASR_OK;
+}
+
+// ---------------------------------------------------------------------------- LM sequence scoring
+// A greedy context, valid arguments (host checks only: nothing has changed when one fails), an attached LM, an idle engine; then
+// lm_score_run (lasr_lm_score.hip.h)
+int lasr_lm_score(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const int32_t* n_tokens, int start, double* total, float* logps) {
+    if (!c) return LASR_EINVAL;
+    if (c->W > 1) return fail(c, LASR_EINVAL, "lasr_lm_score: greedy contexts only (beam = %d)", c->W);
+    if (n < 1 || n > c->d.max_streams) return fail(c, LASR_EINVAL, "bad candidate count (n=%d)", n);
+    if (!slots || !n_tokens || !total) return fail(c, LASR_EINVAL, "null argument");
+    if (start < -1 || start >= c->d.vocab) return fail(c, LASR_EINVAL, "start token %d (-1: none, or 0..%d)", start, c->d.vocab - 1);
+    std::vector<char> seen(c->d.max_streams, 0);
+    for (int i = 0; i < n; ++i) {
+        const int s = slots[i];
+        if (s < 0 || s >= c->d.max_streams || !c->open_[s]) return fail(c, LASR_EINVAL, "slot %d is not open", s);
+        if (seen[s]) return fail(c, LASR_EINVAL, "slot %d listed twice", s);
+        seen[s] = 1;
+    }
+    RC(lat_check_tokens(c, n, tokens, n_tokens));
+    if (!c->lm.on) return fail(c, LASR_ESTATE, "lasr_lm_score: no LM is attached");
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    HIPCHK(c, hipSetDevice(c->device));
+    return lm_score_run(c, slots, n, tokens, n_tokens, start, total, logps);
 }
 
 // Transducer.transcribe_stream on feature chunks (models.py:506-575): carried encoder / predictor

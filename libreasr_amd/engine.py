@@ -767,6 +767,25 @@ class Engine:
         cat, nf = self._cat_feats(feats_list)
         return self._score(self.lib.lasr_score_feats, slots_per_utt, cat, nf, cand_lists, viterbi, lattice)
 
+    def lm_score(self, slots, token_lists, start=None):
+        """log P_LM of every candidate by the attached LM (lasr_lm_score): slots[i] = one open slot per candidate (all distinct, its LM
+        row), token_lists[i] = its non-blank ids.  start=None: the LM reads y_1..y_{U-1} and the first label has no term (0); start=id:
+        the LM reads (start, y_1, .., y_{U-1}) and every label has one.  -> per candidate {"total": float, "logps": float32 [U]}.
+        The slots' LM state is left reset (reset(slot, 4)); nothing else changes."""
+        a, p, n = self._slots(slots)
+        assert len(token_lists) == n
+        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
+        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        total = np.zeros(max(n, 1), dtype=np.float64)
+        lp = np.zeros(max(int(nt.sum()), 1), dtype=np.float32)
+        self._chk(self.lib.lasr_lm_score(self.ctx, p, n, _ptr(tok), _ptr(nt), -1 if start is None else int(start), _ptr(total), _ptr(lp)))
+        out, o = [], 0
+        for i in range(n):
+            out.append({"total": float(total[i]), "logps": lp[o:o + int(nt[i])].copy()})
+            o += int(nt[i])
+        return out
+
     def lattice_tree_dp(self, blank, emit, parent, viterbi=True):
         """The tree dynamic programme alone (lasr_lattice_tree_dp) on caller-supplied lattices: blank / emit = lists of [T_i, N_i]
         float32 arrays (emit[:, 0] is not read), parent = lists of N_i node ids (-1 at node 0, parent[v] < v, depth
