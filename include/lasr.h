@@ -74,7 +74,10 @@ typedef struct {
                          /* lasr_fetch_nbest: the whole beam with per-token frame and     */
                          /* log p.  Both protocols (the                                   */
                          /* pipelined one: <= 512 stream slots); an attached LM is fused  */
-                         /* inside the beam (see lasr_attach_lm).                         */
+                         /* inside the beam (see lasr_attach_lm).  lasr_set_beam_merge:  */
+                         /* hypotheses that hold the same tokens are merged; a score is  */
+                         /* then the log of the summed probability of the alignments     */
+                         /* merged into the hypothesis, not of one alignment.            */
 } lasr_model_desc;
 
 /* Fills `d` with the reference defaults listed above (4x1024 encoder, 2xNBRC predictor). */
@@ -218,7 +221,8 @@ int lasr_step_feats(lasr_ctx* c, const int* slots, int n, const float* feats, in
 /* New tokens of `slot` since the last fetch (int32 ids incl. nothing for blanks); with beam > 1
  * the complete best hypothesis as of the last model step (empty if no step ran since the last fetch).
  * neg_logp / align (optional): offline metrics of the last lasr_transcribe_* call
- * (-sum log p of every decision, models.py:420-422,455; alignment_score, models.py:445-453). */
+ * (-sum log p of every decision, models.py:420-422,455; alignment_score, models.py:445-453).
+ * beam > 1 with lasr_set_beam_merge on: neg_logp = -log of the SUMMED probability of the alignments merged into the hypothesis. */
 int lasr_fetch(lasr_ctx* c, int slot, int32_t* tokens, int cap, int* n_new, double* neg_logp,
                double* align);
 
@@ -262,7 +266,9 @@ int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* token
  * result that was not fetched), and drops the cached decode graphs. */
 int lasr_set_beam_records(lasr_ctx* c, int on);
 /* lasr_fetch for a beam context, whole beam: consumes what lasr_fetch would have consumed.  Up to max_hyps hypotheses, best first
- * (score descending, then slot ascending); no merging: two hypotheses may hold the same tokens on different frames.
+ * (score descending, then slot ascending); no merging: two hypotheses may hold the same tokens on different frames (unless
+ * lasr_set_beam_merge is on: then the hypotheses are pairwise distinct, and scores[i] is the log of the summed probability of the
+ * alignments merged into hypothesis i, while its frames / logps are those of the best-ranked alignment among them).
  * tokens / frames / logps: [max_hyps][cap] (frames, logps optional); n_tokens [max_hyps]; scores [max_hyps] = sum of log p of every
  * decision incl. blanks (scores[0] == -neg_logp of lasr_fetch); *n_hyps = hypotheses alive (may exceed max_hyps: the rest is dropped).
  * Hypothesis 0 is exactly what lasr_fetch returns.  With max_hyps > 0, tokens, n_tokens and scores are required (LASR_EINVAL if null);
@@ -271,6 +277,26 @@ int lasr_set_beam_records(lasr_ctx* c, int on);
  * lasr_fetch / lasr_fetch_many keep working on such a context: they drop the rest of the beam with the result they hand out. */
 int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32_t* frames, float* logps, int cap,
                      int* n_tokens, double* scores, int* n_hyps);
+
+/* ---- Beam search (beam > 1): merging of hypotheses that hold the same tokens.
+ * Without it the beam keeps alignments: up to W - 1 of its W slots may hold a transcript the beam already holds.  While on, after the W
+ * survivors of a selection round are known (same candidates, same order as without), the survivors that hold the same token list since
+ * the stream's last predictor reset AND are in the same state on the current frame (still expanding it / done with it) are merged: the
+ * best-ranked one stays -- with its predictor state, frames and log p -- and its score becomes log(sum of exp(score)) over the group;
+ * the others become dead slots.  At the end of every frame, hence of every model step, the live hypotheses are pairwise distinct.
+ * Equality is decided on (length, 64-bit hash) of the token list (splitmix64 chain over the tokens): a collision would merge two
+ * different lists of the same length; none occurs on the test inputs (checked against the lists themselves on the CPU).
+ * scores / neg_logp change their meaning as said at lasr_fetch and lasr_fetch_nbest; a score may exceed the score of the same tokens
+ * without merging, never the lattice total lasr_align_* reports for them -- except for a hypothesis that put max_iters tokens on one
+ * frame, as described at lasr_align_pcm.  Switch-off keeps the scores as they are; the beam may hold duplicates again from then on.
+ * Allocations, kernels and results of a context that never turns it on are untouched.
+ * beam > 1 only (LASR_EINVAL on a greedy context).  Default off; independent of lasr_set_beam_records.  A call that changes nothing
+ * returns LASR_OK at once; a switch needs an idle context (LASR_ESTATE while a submitted step is uncollected or a slot holds a result
+ * that was not fetched), drops the cached decode graphs, and may happen in mid-stream.
+ * NOT with an LM: LASR_ESTATE (nothing changed) when switching on with an LM attached, and from lasr_attach_lm / lasr_attach_lm_int8
+ * while the switch is on -- the fuser re-picks the token after the selection round, so the identity of the round would be of the
+ * wrong token.  Merging under LM fusion is the follow-up. */
+int lasr_set_beam_merge(lasr_ctx* c, int on);
 
 /* ---- Forced alignment and transcript scoring: the teacher-forced RNN-T lattice.  Replaces Transducer.forward (models.py:308-359:
  * log_softmax(joint(pred[u], enc[t])) for every (t, u)) followed by the forward algorithm of the loss (loss.py:77-79), for inference:

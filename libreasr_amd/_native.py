@@ -70,6 +70,7 @@ SYMBOLS = [
                                      C.POINTER(C.c_double)]),
     ("lasr_fetch_many_aligned", C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, _P]),
     ("lasr_set_beam_records", C.c_int, [_P, C.c_int]),
+    ("lasr_set_beam_merge", C.c_int, [_P, C.c_int]),
     ("lasr_fetch_nbest", C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.POINTER(C.c_int)]),
     ("lasr_align_pcm", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_align_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

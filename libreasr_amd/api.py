@@ -72,18 +72,32 @@ class LibreASR:
             raise ValueError("nbest must be >= 1")
         self.engine.set_beam_records(True)
 
+    def _want_merge(self, merge):
+        """merge=None leaves the engine's switch alone, True / False set it (lasr_set_beam_merge; beam search only)."""
+        if merge is None:
+            return
+        if self.engine.beam <= 1:
+            raise ValueError("merge= needs a beam engine (beam > 1)")
+        self.engine.set_beam_merge(bool(merge))
+
     def _nbest(self, slot, k):
-        """-> up to k hypotheses, best first: {"score": sum of log p of every decision, "tokens": [(token_id, time_s, confidence)]}"""
+        """-> up to k hypotheses, best first: {"score": sum of log p of every decision, "tokens": [(token_id, time_s, confidence)]}.
+        With merging on (merge=True, Engine.set_beam_merge) the hypotheses are pairwise distinct and "score" is the log of the SUMMED
+        probability of the alignments that were merged into the hypothesis; its times and confidences are those of the best-ranked
+        alignment among them."""
         return [{"score": sc, "tokens": self._aligned(t, f, lp)} for t, f, lp, sc in self.engine.fetch_nbest(slot, int(k))]
 
-    def transcribe(self, audio, return_ids=False, return_alignment=False, nbest=None):
+    def transcribe(self, audio, return_ids=False, return_alignment=False, nbest=None, merge=None):
         """Whole utterance(s): fresh state, greedy, max_iters_offline (Transcribe RPC, api-server.py:64-80).
         return_alignment=True: per utterance a list of (token_id, time_s, confidence) instead of text -- time_s is the start of the
         80 ms encoder frame on which the token was emitted, confidence the joint's probability of that decision.  Greedy decode;
         a beam engine raises NotImplementedError: use nbest=.
         nbest=k (beam engines; ValueError on a greedy one): per utterance up to k hypotheses of the final beam, best first, each
-        {"score": float, "tokens": [(token_id, time_s, confidence)]} with time_s / confidence as above; no merging, no length norm."""
+        {"score": float, "tokens": [(token_id, time_s, confidence)]} with time_s / confidence as above; no merging, no length norm.
+        merge=True / False (beam engines; ValueError on a greedy one) turns the merging of hypotheses that hold the same tokens on /
+        off and the engine keeps the setting; None leaves it as it is.  See _nbest for what "score" means then."""
         batch = audio if isinstance(audio, (list, tuple)) else [audio]
+        self._want_merge(merge)
         if return_alignment:
             self._want_alignment()
         if nbest is not None:
@@ -263,14 +277,16 @@ class LibreASR:
         order = sorted(range(len(score)), key=lambda j: (-score[j], j))
         return {"am": am, "lm": lm, "score": score, "best": order[0] if order else None, "order": order}
 
-    def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None):
+    def stream(self, chunks, return_ids=False, return_alignment=False, nbest=None, merge=None):
         """One stream of client chunks (TranscribeStream RPC, api-server.py:82-134): yields the
         hypothesis so far after every model call.
         return_alignment=True: yields the list of (token_id, time_s, confidence) of the hypothesis so far.  time_s is NOMINAL for a
         stream: the streaming front-end takes each frame from the middle chunk of its 3-chunk window, so frame k * 80 ms is where
         the frame sits in the stream of model frames, not an exact position in the client's audio.
-        nbest=k (beam engines): yields up to k hypotheses of the beam after that model call, as transcribe(nbest=k) returns them."""
+        nbest=k (beam engines): yields up to k hypotheses of the beam after that model call, as transcribe(nbest=k) returns them.
+        merge=: as for transcribe."""
         eng = self.engine
+        self._want_merge(merge)
         if return_alignment:
             self._want_alignment()
         if nbest is not None:

@@ -11,10 +11,14 @@ void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_sl
     const float* lg = (const float*)c->logits;
     // one wave per hypothesis row (k_beam_select_rw; V <= 2048 is checked at lasr_create for beam > 1)
     // (b.rec: per-token records, lasr_set_beam_records -- an instantiation of their own, so "off" runs the kernel it always ran)
-    with_const<0, 1>(b.rec ? 1 : 0, [&](auto rec) {
-        with_const<2, 4, 8>(c->W, [&](auto wt) {
-            constexpr int WT = decltype(wt)::value;
-            hipLaunchKernelGGL((k_beam_select_rw<WT, decltype(rec)::value != 0>), dim3(M), dim3(64 * WT), 0, v.stream, lg, b, iter_slot);
+    // (b.seq_hash: merging of equal hypotheses, lasr_set_beam_merge -- likewise)
+    with_const<0, 1>(b.seq_hash ? 1 : 0, [&](auto mrg) {
+        with_const<0, 1>(b.rec ? 1 : 0, [&](auto rec) {
+            with_const<2, 4, 8>(c->W, [&](auto wt) {
+                constexpr int WT = decltype(wt)::value;
+                hipLaunchKernelGGL((k_beam_select_rw<WT, decltype(rec)::value != 0, decltype(mrg)::value != 0>), dim3(M), dim3(64 * WT), 0,
+                                   v.stream, lg, b, iter_slot);
+            });
         });
     });
     if (c->lm.on)

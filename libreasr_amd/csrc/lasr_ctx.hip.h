@@ -80,6 +80,12 @@ struct lasr_ctx {
     BeamRec* rec_host = nullptr;                             // pinned: its copy, once per step
     int rec_slots = 0;                                       // rounds both were sized for (== n_iter_slots while the switch is on, else 0)
     BeamRec *b_rec_ring_host = nullptr, *b_rec_ring_dev = nullptr;   // pinned [TRING][Md], beside b_tre_host (allocated at the first switch-on)
+    // merging of hypotheses that hold the same tokens (lasr_set_beam_merge).  Off (the default): BeamState::seq_hash
+    // null, the kernels of before.  The identities live in one device block, [Md] hashes then [Md] lengths, allocated at the first
+    // switch-on and kept: k_reset_rows restarts them with the predictor from then on, a later switch-on uploads them afresh.
+    bool beam_merge_on = false;
+    unsigned long long* b_seq_hash = nullptr;                // device [Md]
+    int* b_seq_len = nullptr;                                // device [Md], behind the hashes in the same block
     std::vector<long long> b_frame_off;                      // per stream: global frame cursor minus the slot's own count (set at submit, under mu)
     int* trellis_host = nullptr; size_t trellis_host_ints = 0;
     int enc_par = 0;

@@ -13,6 +13,7 @@ int apply_reset(lasr_ctx* c, const DecView& v, bool any_pred, int mask = 3, bool
     a.what = c->dc.what; a.mask = mask; a.M = c->M; a.MT = c->MT; a.H = c->d.hidden; a.Le = c->d.enc_layers; a.Lp = c->d.pred_layers;
     a.pred_lstm = c->d.pred_cell; a.bos = c->d.bos; a.bf = c->bf;
     a.W = beam ? c->W : 1; a.Md = c->Md; a.score = c->b_score; a.alive = c->b_alive; a.inB = c->b_inB; a.parent = c->b_parent;
+    a.seq_hash = c->b_seq_hash; a.seq_len = c->b_seq_len;          // (null until lasr_set_beam_merge was first turned on)
     for (int l = 0; l < a.Le; ++l) {
         a.enc_h[l] = c->enc_h[c->enc_par][l]; a.enc_c[l] = c->enc_c[l];
         a.enc_h0[l] = c->enc[l].h0; a.enc_c0[l] = c->enc[l].c0;
@@ -224,6 +225,7 @@ BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
     b.W = c->W; b.V = c->d.vocab; b.blank = c->d.blank; b.max_iters = max_iters; b.Md = c->Md;
     b.t_idx = v.t_idx; b.T_row = v.T_row;
     b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit; b.parent = c->b_parent;
+    if (c->beam_merge_on) { b.seq_hash = c->b_seq_hash; b.seq_len = c->b_seq_len; }
     if (!cont) {
         b.iters = c->ds.iters; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
         b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer

@@ -2158,6 +2158,44 @@ int lasr_set_beam_records(lasr_ctx* c, int on) {
     return LASR_OK;
 }
 
+// ---------------------------------------------------------------------------- beam: merging of equal hypotheses
+// k_beam_select_rw<WT, REC, true> keeps an identity per slot (BeamState::seq_hash / seq_len; null = off, the default: the
+// <WT, REC, false> instantiation) and merges the survivors of a round that hold the same tokens.  Like the records
+// switch this changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  At a
+// switch-on in mid-stream the identities come from the host: the engine is idle, so every stream's tree holds every live slot's
+// tokens since the frozen prefix (a dead slot, cur = -1, gets the empty identity like an empty list).
+int lasr_set_beam_merge(lasr_ctx* c, int on) {
+    if (!c) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "beam merging serves beam search (beam > 1)");
+    const bool want = on != 0;
+    if (want == c->beam_merge_on) return LASR_OK;     // (nothing to switch: also fine while steps are in flight)
+    if (want && c->lm.on) return fail(c, LASR_ESTATE, "beam merging with an LM attached is not implemented (k_beam_fuse re-picks the token after the selection)");
+    RC(toggle_prologue(c, "slot %d holds a result that was not fetched: fetch it before the switch"));
+    if (want) {
+        const size_t Md = (size_t)c->Md;
+        if (!c->b_seq_hash) {
+            RC(dalloc(c, &c->b_seq_hash, Md + (Md + 1) / 2));         // [Md] 64-bit hashes, then [Md] 32-bit lengths
+            c->b_seq_len = (int*)(c->b_seq_hash + Md);
+        }
+        std::vector<unsigned long long> img(Md + (Md + 1) / 2, 0ull);
+        int* len = (int*)(img.data() + Md);
+        for (int r = 0; r < c->M; ++r) {
+            const BeamHost& B = c->beams[r].tree;
+            for (int j = 0; j < c->W; ++j) {
+                std::vector<int32_t> toks;
+                if (j < (int)B.cur.size()) bh_tokens(B, B.cur[j], toks);
+                uint64_t h = BM_SEED;
+                for (int32_t v : toks) h = bm_append(h, v);
+                img[(size_t)r * c->W + j] = h; len[(size_t)r * c->W + j] = (int)toks.size();
+            }
+        }
+        HIPCHK(c, hipMemcpy(c->b_seq_hash, img.data(), sizeof(unsigned long long) * img.size(), hipMemcpyHostToDevice));
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->beam_merge_on = want;                          // (off: the block stays; the scores stay what they are)
+    return LASR_OK;
+}
+
 int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32_t* frames, float* logps, int cap, int* n_tokens,
                      double* scores, int* n_hyps) {
     if (!c || !n_hyps) return LASR_EINVAL;
@@ -2472,6 +2510,7 @@ static int lm_side_setup(lasr_ctx* c) {
 static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights, bool q8) {
     if (!c) return LASR_EINVAL;
     if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
+    if (c->beam_merge_on) return fail(c, LASR_ESTATE, "beam merging is on: merging under LM fusion is not implemented (lasr_set_beam_merge(c, 0) first)");
     if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)
         return fail(c, LASR_EINVAL, "LM weight blob has %zu floats, expected %zu", n_weights, d ? lasr_lm_weight_count(d) : (size_t)0);

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "lasr_beamhist.hip.h"      // BeamRec (standard C++ only)
+#include "lasr_beam_merge.hip.h"    // identities of beam hypotheses + the merge step of k_beam_select_rw
 
 namespace lasr {
 
@@ -161,6 +162,8 @@ struct ResetArgs {
     int* alive;
     int* inB;
     int* parent;
+    unsigned long long* seq_hash;   // beam merging (lasr_set_beam_merge): the slots' identities restart with the predictor; null
+    int* seq_len;                   //   until the switch is first turned on
     void* enc_h[16];          // current-parity fragment buffers (element-typed)
     float* enc_c[16];
     const float* enc_h0[16];  // [H]
@@ -210,6 +213,7 @@ inline __global__ void k_reset_rows(const ResetArgs a) {
                 a.parent[rp + b] = b;
                 if (b) a.emit[rp + b] = 0;
                 if (wh & 2) { a.score[rp + b] = b ? -INFINITY : 0.0; a.alive[rp + b] = b ? 0 : 1; a.inB[rp + b] = 0; }
+                if ((wh & 2) && a.seq_hash) { a.seq_hash[rp + b] = BM_SEED; a.seq_len[rp + b] = 0; }
             }
     }
     const size_t ho = act_off(a.bf, r, u, a.MT);
@@ -943,6 +947,11 @@ struct BeamState : ContRound {
     // non-blank token gets (frame cursor at entry, the joint's log p of the extension: the f32 term that went into its score);
     // every other entry is stale.  Null = off (k_beam_select_rw<WT, false> never looks).
     BeamRec* rec;        // [n_iter_slots | tring][Md]
+    // merging of hypotheses that hold the same tokens (lasr_set_beam_merge; DESIGN 5.9, lasr_beam_merge.hip.h): every slot's
+    // identity, (length, hash) of its token list since the stream's last predictor reset.  Null = off (k_beam_select_rw<WT, REC,
+    // false> never looks).
+    unsigned long long* seq_hash;   // [Md]
+    int* seq_len;                   // [Md]
 };
 
 // k_beam_select with ONE WAVE PER HYPOTHESIS ROW (V <= 2048, the 512-thread form's arithmetic): wave b keeps row b's logits in
@@ -955,7 +964,9 @@ struct BeamState : ContRound {
 // algorithm returns the same list.  (A row's candidates in the global top-W are its best by log p: the score offset is per row.)
 // REC (records on): a third WT x WT table carries every candidate's f32 term to wave 0 beside its score and ordinal; the slots wave
 // 0 extends store (t, term) into s.rec.  REC = false is the kernel as it was.
-template <int WT, bool REC>
+// MERGE (lasr_set_beam_merge): between the selection of the W survivors and their stores, wave 0 merges the survivors that hold the
+// same tokens (beam_merge_round); a merged-away slot takes the dead-slot path of the stores.  MERGE = false is the kernel as it was.
+template <int WT, bool REC, bool MERGE>
 __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restrict__ logits, BeamState s, int iter_slot) {
     constexpr int VW = 8, KEEP = 4, NTV = 512;      // virtual waves / slots per virtual thread / virtual threads (the old layout)
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1112,6 +1123,10 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     __syncthreads();
     if (w != 0) return;
     if (dbg) s.dbg[9] = wall_clock64();
+    // (MERGE) this lane's own slot's identity at the start of the round, in registers before any lane stores anything
+    unsigned long long id_hash = BM_SEED;
+    int id_len = 0;
+    if constexpr (MERGE) { if (lane < W) { id_hash = s.seq_hash[r0 + lane]; id_len = s.seq_len[r0 + lane]; } }
     // ---- the ordered top-W of the WT x WT candidate table, by wave 0 (round 6; one thread before: W passes over W list heads + W
     // slots of bookkeeping = 3.1 us of 7.6 at W = 4, 7.6 of 13.3 at W = 8).  Lane l holds candidate (row l / WT, position l % WT); its
     // rank = the number of candidates that come before it in the total order (score descending, ordinal ascending: ordinals are
@@ -1146,7 +1161,9 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     }
     if (dbg) s.dbg[3] = wall_clock64();
     const int round = s.iters[q] + 1;
-    const bool slot = lane < W, live = slot && sel > -INFINITY;
+    const bool slot = lane < W;
+    bool live = slot && sel > -INFINITY;
+    if constexpr (MERGE) beam_merge_round<WT>(lane, W, V, s.blank, round >= s.max_iters, id_hash, id_len, sord, live, sel, s.seq_hash + r0, s.seq_len + r0);
     int inb = 1;
     if (slot) {
         const int r = r0 + lane;

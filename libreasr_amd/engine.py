@@ -329,6 +329,13 @@ class Engine:
         switch, the engine must be idle (no submitted step uncollected, no result unfetched).  beam = 1: LasrError (LASR_EINVAL)."""
         self._chk(self.lib.lasr_set_beam_records(self.ctx, 1 if on else 0))
 
+    def set_beam_merge(self, on=True):
+        """Merging of beam hypotheses that hold the same tokens (lasr_set_beam_merge): off by default.  While on, the live hypotheses
+        are pairwise distinct after every frame and a score is the log of the summed probability of the alignments merged into the
+        hypothesis.  To switch, the engine must be idle; not with an LM attached (LasrError, LASR_ESTATE).  beam = 1: LasrError
+        (LASR_EINVAL)."""
+        self._chk(self.lib.lasr_set_beam_merge(self.ctx, 1 if on else 0))
+
     def fetch_nbest(self, slot, max_hyps=None, cap=65536):
         """fetch(slot) for the whole beam -> [(tokens, frames, logps, score)], best first (score descending, then hypothesis slot
         ascending; no merging): up to max_hyps (default: the beam width) of the hypotheses alive after the last model step.
