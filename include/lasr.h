@@ -293,9 +293,29 @@ int lasr_fetch_nbest(lasr_ctx* c, int slot, int max_hyps, int32_t* tokens, int32
  * beam > 1 only (LASR_EINVAL on a greedy context).  Default off; independent of lasr_set_beam_records.  A call that changes nothing
  * returns LASR_OK at once; a switch needs an idle context (LASR_ESTATE while a submitted step is uncollected or a slot holds a result
  * that was not fetched), drops the cached decode graphs, and may happen in mid-stream.
- * NOT with an LM: LASR_ESTATE (nothing changed) when switching on with an LM attached, and from lasr_attach_lm / lasr_attach_lm_int8
- * while the switch is on -- the fuser re-picks the token after the selection round, so the identity of the round would be of the
- * wrong token.  Merging under LM fusion is the follow-up. */
+ * on = 1 is NOT for an LM: LASR_ESTATE (nothing changed) when switching to 1 with an LM attached, and from lasr_attach_lm /
+ * lasr_attach_lm_int8 while the switch is 1 -- the fuser re-picks the token after the selection round, so the identity of the round
+ * would be of the wrong token.  Merging under LM fusion is a mode of its own:
+ *
+ * on = LASR_BEAM_MERGE_LM.  Without an LM attached it is on = 1 exactly (same kernels, bit-equal results).  With an LM attached
+ * (lasr_attach_lm is accepted while this mode is on; lasr_attach_lm_int8 stays refused on a beam context) the rule above holds with
+ * one change: a slot's identity is chained from the token the slot actually CARRIES after the round -- for a slot extended by a
+ * non-blank token the fuser's re-pick where the parent's LM has advanced since its last reset, the joint's token otherwise -- and the
+ * merge step runs on the round's W survivors AFTER the re-pick.  Everything else is as above: groups by (length, hash, state on the
+ * frame); the lowest slot stays with its parent, token, predictor state, LM state, LM output, frames and log p (the log p of a record
+ * stays the joint's term); its score becomes the log-sum over the group in ascending slot order; the others become dead slots; slots
+ * are not compacted.  Everything a fetch returns describes the state after the merge.
+ * What a score means in this mode: the term the beam adds for an emitted token is the joint's log p of its best non-blank token, not
+ * of the token the fuser emitted, so a merged score is the log of a sum of such products and NOT log P(tokens | audio): the bound by
+ * the lattice total of lasr_align_* is not claimed in this mode.
+ * The LM state of a merged hypothesis is the kept slot's.  The members of a group hold the same tokens since the last predictor reset
+ * behind the same frozen prefix, so they have fed the LM the same tokens -- except after lasr_stream_reset with bit 4 and without
+ * bit 2 (LM reset, predictor kept): two equal token lists may then have fed the LM different suffixes; the kept slot's LM state and
+ * its "has advanced" flag win.
+ * Switches 0 <-> LASR_BEAM_MERGE_LM and 1 <-> LASR_BEAM_MERGE_LM are switches like 0 <-> 1 (idle context, results fetched, graphs
+ * dropped, possible in mid-stream); with an LM attached LASR_BEAM_MERGE_LM -> 1 is LASR_ESTATE and changes nothing.  Any other
+ * nonzero value of `on` means 1. */
+#define LASR_BEAM_MERGE_LM 2   /* lasr_set_beam_merge(c, LASR_BEAM_MERGE_LM) */
 int lasr_set_beam_merge(lasr_ctx* c, int on);
 
 /* ---- Forced alignment and transcript scoring: the teacher-forced RNN-T lattice.  Replaces Transducer.forward (models.py:308-359:

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LASR_LIB") or os.path.join(_HERE, "csrc", "liblasr_hip.so")   # LASR_LIB: A/B builds
 
 LASR_OK, LASR_EINVAL, LASR_ENOMEM, LASR_EHIP, LASR_ESTATE, LASR_EFULL = 0, -1, -2, -3, -4, -5
+LASR_BEAM_MERGE_LM = 2          # lasr_set_beam_merge(c, LASR_BEAM_MERGE_LM): merging of equal hypotheses also under LM fusion
 LASR_PUSH_PINNED_NOCOPY = 1
 LASR_PUSH_DEVICE_STABLE = 2
 LASR_RESET_IF_DECODED = 16

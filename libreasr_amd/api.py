@@ -73,12 +73,18 @@ class LibreASR:
         self.engine.set_beam_records(True)
 
     def _want_merge(self, merge):
-        """merge=None leaves the engine's switch alone, True / False set it (lasr_set_beam_merge; beam search only)."""
+        """merge=None leaves the engine's switch alone, True / False set it (lasr_set_beam_merge; beam search only); "lm" selects
+        LASR_BEAM_MERGE_LM, the mode that also merges with an LM attached (synthetic_lm= / conf["lm"])."""
         if merge is None:
             return
         if self.engine.beam <= 1:
             raise ValueError("merge= needs a beam engine (beam > 1)")
-        self.engine.set_beam_merge(bool(merge))
+        if isinstance(merge, str):
+            if merge != "lm":
+                raise ValueError('merge= takes None, True, False or "lm"')
+            self.engine.set_beam_merge(True, lm=True)
+        else:
+            self.engine.set_beam_merge(bool(merge))
 
     def _nbest(self, slot, k):
         """-> up to k hypotheses, best first: {"score": sum of log p of every decision, "tokens": [(token_id, time_s, confidence)]}.
@@ -95,7 +101,9 @@ class LibreASR:
         nbest=k (beam engines; ValueError on a greedy one): per utterance up to k hypotheses of the final beam, best first, each
         {"score": float, "tokens": [(token_id, time_s, confidence)]} with time_s / confidence as above; no merging, no length norm.
         merge=True / False (beam engines; ValueError on a greedy one) turns the merging of hypotheses that hold the same tokens on /
-        off and the engine keeps the setting; None leaves it as it is.  See _nbest for what "score" means then."""
+        off and the engine keeps the setting; None leaves it as it is.  See _nbest for what "score" means then.  merge=True raises
+        on an engine with an LM attached; merge="lm" merges there too (identities follow the LM fuser's re-picked tokens; a score is
+        then a log-sum of products of the joint's terms, not log P(tokens | audio)) and is merge=True on an engine without an LM."""
         batch = audio if isinstance(audio, (list, tuple)) else [audio]
         self._want_merge(merge)
         if return_alignment:

@@ -3,7 +3,7 @@
 // (0, BM_SEED), appending token v gives (len + 1, bm_mix(hash ^ (v + 1))).  bm_mix is the splitmix64 finaliser, a bijection: the
 // extensions of one parent by different tokens never share a hash.  The first part is plain C++ (the host computes the identities
 // of a running stream at switch-on: lasr_engine.hip); the device routine below is what wave 0 of k_beam_select_rw<WT, REC, true>
-// calls between the selection of a round's W survivors and their stores.
+// calls between the selection of a round's W survivors and their stores; beam_merge_repicked behind it is k_beam_fuse_merge's.
 #pragma once
 
 #include <cstdint>
@@ -66,6 +66,45 @@ __device__ __forceinline__ void beam_merge_round(const int lane, const int W, co
     if (live) { nh = em ? bm_append(ph, k - 1) : ph; nl = pl + (em ? 1 : 0); }
     // groups: lane j's key is broadcast in turn; a lower live lane with my key takes me in, a higher one is folded into my score
     // (ascending j: the fold's order).  lae runs only in rounds that merge something (wave-uniform test).
+    const double own_sel = sel;
+    double acc = sel;
+    bool gone = false;
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+        const uint64_t h = bm_readlane64(nh, j);
+        const int l = __builtin_amdgcn_readlane(nl, j);
+        const int fl = __builtin_amdgcn_readlane((live ? 2 : 0) | inb, j);
+        const double sc = bm_readlane_f64(own_sel, j);
+        const bool same = live && j != lane && (fl & 2) && (fl & 1) == inb && l == nl && h == nh;
+        if (__ballot(same) == 0ull) continue;
+        if (same && j < lane) gone = true;
+        if (same && j > lane) acc = bm_lae(acc, sc);
+    }
+    if (gone) { live = false; nh = BM_SEED; nl = 0; }
+    sel = live ? acc : -INFINITY;
+    if (lane < W) { hash_row[lane] = nh; len_row[lane] = nl; }
+}
+
+// The same step for k_beam_fuse_merge (merging under LM fusion, LASR_BEAM_MERGE_LM), which runs BEHIND the selection
+// kernel and the fuser's re-pick: the survivor comes as the selection kernel stored it -- pb (its parent slot), em (extended by a
+// non-blank token), inb (its state on the frame after the round) -- with tok = the token the slot carries after the re-pick.
+// Everything else as above.  (A routine of its own, not beam_merge_round's core: k_beam_select_rw<WT, REC, true> keeps the
+// instruction stream it had.)
+template <int WT>
+__device__ __forceinline__ void beam_merge_repicked(const int lane, const int W, const int pb, const bool em, const int tok, const int inb,
+                                                    const uint64_t own_hash, const int own_len, bool& live, double& sel,
+                                                    unsigned long long* __restrict__ hash_row, int* __restrict__ len_row) {
+    uint64_t ph = BM_SEED;
+    int pl = 0;
+#pragma unroll
+    for (int j = 0; j < WT; ++j) {
+        const uint64_t h = bm_readlane64(own_hash, j);
+        const int l = __builtin_amdgcn_readlane(own_len, j);
+        if (pb == j) { ph = h; pl = l; }
+    }
+    uint64_t nh = BM_SEED;
+    int nl = 0;
+    if (live) { nh = em ? bm_append(ph, tok) : ph; nl = pl + (em ? 1 : 0); }
     const double own_sel = sel;
     double acc = sel;
     bool gone = false;

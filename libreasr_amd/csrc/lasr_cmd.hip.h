@@ -11,8 +11,10 @@ void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_sl
     const float* lg = (const float*)c->logits;
     // one wave per hypothesis row (k_beam_select_rw; V <= 2048 is checked at lasr_create for beam > 1)
     // (b.rec: per-token records, lasr_set_beam_records -- an instantiation of their own, so "off" runs the kernel it always ran)
-    // (b.seq_hash: merging of equal hypotheses, lasr_set_beam_merge -- likewise)
-    with_const<0, 1>(b.seq_hash ? 1 : 0, [&](auto mrg) {
+    // (b.seq_hash: merging of equal hypotheses, lasr_set_beam_merge -- likewise.  With an LM attached the identities are of the
+    //  re-picked tokens: the selection kernel runs its MERGE = false body and k_beam_fuse_merge re-picks, merges and patches)
+    const bool fuse_merge = c->lm.on && b.seq_hash;
+    with_const<0, 1>(b.seq_hash && !fuse_merge ? 1 : 0, [&](auto mrg) {
         with_const<0, 1>(b.rec ? 1 : 0, [&](auto rec) {
             with_const<2, 4, 8>(c->W, [&](auto wt) {
                 constexpr int WT = decltype(wt)::value;
@@ -21,7 +23,14 @@ void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_sl
             });
         });
     });
-    if (c->lm.on)
+    if (fuse_merge)
+        with_const<8, 16>(keep16(c->d.vocab) ? 16 : 8, [&](auto keep) {
+            with_const<2, 4, 8>(c->W, [&](auto wt) {
+                hipLaunchKernelGGL((k_beam_fuse_merge<decltype(wt)::value, decltype(keep)::value>), dim3(M), dim3(256), 0, v.stream, lg, b, iter_slot,
+                                   (const float*)c->lm.lmz[lp], (const int*)c->lm.valid[lp], c->lm.alpha, c->lm.theta, c->lm.min_val);
+            });
+        });
+    else if (c->lm.on)
         with_const<8, 16>(keep16(c->d.vocab) ? 16 : 8, [&](auto keep) {
             hipLaunchKernelGGL(k_beam_fuse<decltype(keep)::value>, dim3(c->Md), dim3(256), 0, v.stream, lg, b, iter_slot, (const float*)c->lm.lmz[lp],
                                (const int*)c->lm.valid[lp], c->lm.alpha, c->lm.theta, c->lm.min_val);

@@ -83,7 +83,9 @@ struct lasr_ctx {
     // merging of hypotheses that hold the same tokens (lasr_set_beam_merge).  Off (the default): BeamState::seq_hash
     // null, the kernels of before.  The identities live in one device block, [Md] hashes then [Md] lengths, allocated at the first
     // switch-on and kept: k_reset_rows restarts them with the predictor from then on, a later switch-on uploads them afresh.
-    bool beam_merge_on = false;
+    // beam_merge: 0 off, 1 on (refuses an LM), LASR_BEAM_MERGE_LM on and also under LM fusion (with an LM attached
+    // k_beam_fuse_merge takes k_beam_fuse's place; without one the mode runs mode 1's kernels).
+    int beam_merge = 0;
     unsigned long long* b_seq_hash = nullptr;                // device [Md]
     int* b_seq_len = nullptr;                                // device [Md], behind the hashes in the same block
     std::vector<long long> b_frame_off;                      // per stream: global frame cursor minus the slot's own count (set at submit, under mu)

@@ -225,7 +225,7 @@ BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
     b.W = c->W; b.V = c->d.vocab; b.blank = c->d.blank; b.max_iters = max_iters; b.Md = c->Md;
     b.t_idx = v.t_idx; b.T_row = v.T_row;
     b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit; b.parent = c->b_parent;
-    if (c->beam_merge_on) { b.seq_hash = c->b_seq_hash; b.seq_len = c->b_seq_len; }
+    if (c->beam_merge) { b.seq_hash = c->b_seq_hash; b.seq_len = c->b_seq_len; }
     if (!cont) {
         b.iters = c->ds.iters; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
         b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer

@@ -2163,15 +2163,19 @@ int lasr_set_beam_records(lasr_ctx* c, int on) {
 // <WT, REC, false> instantiation) and merges the survivors of a round that hold the same tokens.  Like the records
 // switch this changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  At a
 // switch-on in mid-stream the identities come from the host: the engine is idle, so every stream's tree holds every live slot's
-// tokens since the frozen prefix (a dead slot, cur = -1, gets the empty identity like an empty list).
+// tokens since the frozen prefix (a dead slot, cur = -1, gets the empty identity like an empty list).  With an LM attached those
+// are the re-picked tokens (k_beam_fuse patches the trellis), which is what LASR_BEAM_MERGE_LM chains its identities from.
 int lasr_set_beam_merge(lasr_ctx* c, int on) {
     if (!c) return LASR_EINVAL;
     if (c->W <= 1) return fail(c, LASR_EINVAL, "beam merging serves beam search (beam > 1)");
-    const bool want = on != 0;
-    if (want == c->beam_merge_on) return LASR_OK;     // (nothing to switch: also fine while steps are in flight)
-    if (want && c->lm.on) return fail(c, LASR_ESTATE, "beam merging with an LM attached is not implemented (k_beam_fuse re-picks the token after the selection)");
+    // three modes: 0 off, 1 on, LASR_BEAM_MERGE_LM on and also under LM fusion (k_beam_fuse_merge); any other value is 1
+    const int want = on == 0 ? 0 : (on == LASR_BEAM_MERGE_LM ? LASR_BEAM_MERGE_LM : 1);
+    if (want == c->beam_merge) return LASR_OK;        // (nothing to switch: also fine while steps are in flight)
+    if (want == 1 && c->lm.on)
+        return fail(c, LASR_ESTATE, "lasr_set_beam_merge(c, 1) refuses an attached LM (the identity of the selection round would be of the token "
+                                    "k_beam_fuse re-picks afterwards): LASR_BEAM_MERGE_LM merges under LM fusion");
     RC(toggle_prologue(c, "slot %d holds a result that was not fetched: fetch it before the switch"));
-    if (want) {
+    if (want && !c->beam_merge) {                     // (1 <-> LASR_BEAM_MERGE_LM: both modes keep the identities up to date)
         const size_t Md = (size_t)c->Md;
         if (!c->b_seq_hash) {
             RC(dalloc(c, &c->b_seq_hash, Md + (Md + 1) / 2));         // [Md] 64-bit hashes, then [Md] 32-bit lengths
@@ -2192,7 +2196,7 @@ int lasr_set_beam_merge(lasr_ctx* c, int on) {
         HIPCHK(c, hipMemcpy(c->b_seq_hash, img.data(), sizeof(unsigned long long) * img.size(), hipMemcpyHostToDevice));
     }
     std::lock_guard<std::mutex> lk(c->mu);
-    c->beam_merge_on = want;                          // (off: the block stays; the scores stay what they are)
+    c->beam_merge = want;                             // (off: the block stays; the scores stay what they are)
     return LASR_OK;
 }
 
@@ -2510,7 +2514,7 @@ static int lm_side_setup(lasr_ctx* c) {
 static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights, bool q8) {
     if (!c) return LASR_EINVAL;
     if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
-    if (c->beam_merge_on) return fail(c, LASR_ESTATE, "beam merging is on: merging under LM fusion is not implemented (lasr_set_beam_merge(c, 0) first)");
+    if (c->beam_merge == 1) return fail(c, LASR_ESTATE, "beam merging is on in the mode that refuses an LM (lasr_set_beam_merge(c, 0) or (c, LASR_BEAM_MERGE_LM) first)");
     if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)
         return fail(c, LASR_EINVAL, "LM weight blob has %zu floats, expected %zu", n_weights, d ? lasr_lm_weight_count(d) : (size_t)0);

@@ -1369,6 +1369,132 @@ __global__ __launch_bounds__(256) void k_beam_fuse(const float* __restrict__ log
     if (tid == 0) cont_arrive(s, rd, s.done2, false, true);
 }
 
+// k_beam_fuse's re-pick as a routine, for k_beam_fuse_merge below: the same statements in the same order (the joint's log-softmax
+// statistics in k_beam_fuse's thread layout, then lm_standardise and lm_fused_argmax themselves), hence the same token from the same
+// inputs.  (k_beam_fuse keeps its own copy: its instruction stream stays what it was.)  By a workgroup of 256 threads: z = the
+// PARENT's logits row, lz = the parent's LM output.  Every thread returns the token.  sh4 / sv / si: 4 words of LDS each; they may still be read from an earlier call (the first store to each sits behind
+// a barrier that every reader of the earlier call has passed).
+template <int KEEP>
+__device__ __forceinline__ int beam_repick(const float* __restrict__ z, const float* __restrict__ lz, float alpha, float theta, float lm_min,
+                                           int V, float* sh4, float* sv, int* si, int tid) {
+    const int lane = tid & 63, w = tid >> 6;
+    float zv[KEEP];
+    float best = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) {
+        const int j = tid + 256 * k;
+        zv[k] = j < V ? z[j] : -INFINITY;
+        best = fmaxf(best, zv[k]);
+    }
+    best = wave_max_f32(best);
+    if (lane == 0) sh4[w] = best;
+    __syncthreads();
+    best = fmaxf(fmaxf(sh4[0], sh4[1]), fmaxf(sh4[2], sh4[3]));
+    float part = 0.f;
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) part += expf(zv[k] - best);
+    part = wave_sum_f32(part);
+    __syncthreads();
+    if (lane == 0) sh4[w] = part;
+    __syncthreads();
+    const float lse = logf(sh4[0] + sh4[1] + sh4[2] + sh4[3]);     // (same sums as k_select's: the joint log-softmax the greedy fuser sees)
+    const float den = lm_standardise<KEEP>(zv, best, lse, V, sh4, tid);
+    return lm_fused_argmax<KEEP>(zv, den, lz, alpha, theta, lm_min, V, sv, si, tid);
+}
+
+// Merging of equal hypotheses under LM fusion (lasr_set_beam_merge(c, LASR_BEAM_MERGE_LM) with an LM attached): takes
+// k_beam_fuse's place behind k_beam_select_rw<WT, REC, false>.  A slot's identity is chained from the token the slot carries AFTER
+// the round, which for an extended slot is the fuser's re-pick -- so the merge needs all W re-picked tokens of a stream and runs
+// here, ONE WORKGROUP PER STREAM, on what the selection kernel stored:
+//   1. re-pick: the stream's extended slots in turn, each by the whole workgroup with k_beam_fuse's own routine (beam_repick: its
+//      thread layout and summation order, hence its tokens); lane j of wave 0 keeps slot j's token;
+//   2. merge: wave 0, beam_merge_repicked on the round's survivors as the selection kernel stored them (score, alive, parent, emit) and
+//      the identities of the round's start (the selection kernel's MERGE = false body never touches them);
+//   3. patch: a re-picked slot's token and trellis word as k_beam_fuse patches them; a kept slot's score; a merged-away slot becomes
+//      the dead slot of 5.9 (alive 0, emit 0, parent = own lane, score -inf, inB 0, trellis -2) -- the predictor chain, the LM step
+//      and the carry read emit / parent / token behind this launch; end_score / end_alive of a model step that finished in this
+//      round are rewritten in place (pinned memory nobody reads before the publication below);
+//   4. publish: the round goes to the host through done2, once, behind all of these stores, as from k_beam_fuse.
+// The round as the selection kernel left it: iters[q] == 0 iff every live survivor was in B (all_b: the frame ended, inB was cleared
+// and t_idx moved on) -- then the round's inB is 1 for every live slot and a model step ended iff t_idx % step_T == 0; otherwise
+// the round's inB is what inB holds.  Two facts make patching enough:
+//   * all_b is invariant under the merge: a group shares inB, so a merge removes no live slot's state from the frame without leaving
+//     one of the same state -- t_idx, iters, frame_done, unfinished and host_cur stay as the selection kernel decided them;
+//   * the kept slot's LM state is the group's: the members hold the same tokens since the last predictor reset behind the same frozen
+//     prefix, so they fed the LM the same suffix (exception: a reset with bit 4 and without bit 2, see include/lasr.h).
+// A stream without a frame to decode had an identity round (trellis -1): nothing to re-pick, nothing to merge.  That is told from
+// "finished its last frame in this round" by the trellis word, read only when t_idx has reached T_row (in continuous mode the word
+// is pinned memory).  No workgroup waits for another: the only cross-workgroup traffic is the arrival count.
+template <int WT, int KEEP>
+__global__ __launch_bounds__(256) void k_beam_fuse_merge(const float* __restrict__ logits, BeamState s, int iter_slot,
+                                                         const float* __restrict__ lmz, const int* __restrict__ lm_valid, float alpha,
+                                                         float theta, float lm_min) {
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int W = s.W, V = s.V, r0 = q * W;
+    const ContSlot rd = cont_round(s, iter_slot, s.done2, false, q == 0 && tid == 0);     // (k_beam_select_rw's round: it has moved the counter on)
+    int* tre = s.trellis + (size_t)(s.cont ? rd.no % s.tring : iter_slot) * s.Md + r0;
+    __shared__ float sh4[4];
+    __shared__ float sv[4];
+    __shared__ int si[4];
+    const bool slot = tid < W;                       // wave 0, lane j = slot j
+    const int r = r0 + (slot ? tid : 0);
+    const int pb = slot ? s.parent[r] : 0;
+    const bool em = slot && s.emit[r] != 0;
+    int tok = em ? s.token[r] : 0;
+    bool repicked = false;
+    // ---- 1. the re-picks, slot by slot (uniform over the workgroup).  Every wave takes the list of slots to re-pick from the round
+    // as the selection kernel stored it, in front of a barrier: wave 0 patches emit / parent below while the others may lag.
+    unsigned todo = 0;
+    for (int j = 0; j < W; ++j)
+        if (s.emit[r0 + j] && lm_valid[r0 + s.parent[r0 + j]]) todo |= 1u << j;
+    __syncthreads();
+    for (int j = 0; j < W; ++j) {
+        if (!(todo >> j & 1u)) continue;
+        const int prow = r0 + s.parent[r0 + j];      // (wave 0 is still in this loop: nothing is patched yet)
+        const int fa = beam_repick<KEEP>(logits + (size_t)prow * V, lmz + (size_t)prow * V, alpha, theta, lm_min, V, sh4, sv, si, tid);
+        if (tid == j) { tok = fa; repicked = true; }
+    }
+    if (tid >= 64) return;                           // (no barrier from here on)
+    // ---- 2. the merge
+    const int tn = s.t_idx[q], it = s.iters[q];
+    bool idle = false;
+    if (tn >= s.T_row[q]) idle = __ballot(slot && tre[lane] == -1) != 0ull;
+    if (!idle) {
+        unsigned long long id_hash = BM_SEED;
+        int id_len = 0, inb = 1;
+        bool live = false;
+        double sel = -INFINITY;
+        if (slot) {
+            id_hash = s.seq_hash[r]; id_len = s.seq_len[r];
+            live = s.alive[r] != 0;
+            if (live) sel = s.score[r];
+            if (it != 0) inb = s.inB[r];
+        }
+        const bool was_live = live;
+        const double was_sel = sel;
+        beam_merge_repicked<WT>(lane, W, pb, em, tok, inb, id_hash, id_len, live, sel, s.seq_hash + r0, s.seq_len + r0);
+        // ---- 3. the patches
+        const bool merged = __ballot(was_live && !live) != 0ull;
+        if (slot) {
+            if (was_live && !live) {
+                s.alive[r] = 0; s.emit[r] = 0; s.parent[r] = lane; s.score[r] = -INFINITY; s.inB[r] = 0; tre[lane] = -2;
+            } else if (live) {
+                if (sel != was_sel) s.score[r] = sel;
+                if (repicked) { s.token[r] = tok; tre[lane] = (pb << 16) | (tok + 1); }
+            }
+        }
+        if (merged && s.cont && it == 0 && tn % s.step_T == 0) {      // the model step that just ended: the host reads these
+            const size_t es = (size_t)q * s.end_slots + ((tn / s.step_T - 1) % s.end_slots);
+            if (slot) s.end_score[es * W + lane] = sel;
+            const int am = (int)(__ballot(live) & ((1ull << W) - 1ull));
+            if (lane == 0) s.end_alive[es] = am;
+        }
+    }
+    // ---- 4. every lane orders its own stores towards the host in front of lane 0's arrival
+    if (slot && s.cont && s.host_flag) __threadfence_system();
+    if (lane == 0) cont_arrive(s, rd, s.done2, false, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // front-end: log-mel (TransformTime, transforms.py:306-323) -- framing, Hann window, 1024-point
 // real FFT (as a 512-point complex FFT, radix 8x8x8 in registers + LDS transposes), power,

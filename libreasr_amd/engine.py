@@ -329,12 +329,15 @@ class Engine:
         switch, the engine must be idle (no submitted step uncollected, no result unfetched).  beam = 1: LasrError (LASR_EINVAL)."""
         self._chk(self.lib.lasr_set_beam_records(self.ctx, 1 if on else 0))
 
-    def set_beam_merge(self, on=True):
+    def set_beam_merge(self, on=True, lm=False):
         """Merging of beam hypotheses that hold the same tokens (lasr_set_beam_merge): off by default.  While on, the live hypotheses
         are pairwise distinct after every frame and a score is the log of the summed probability of the alignments merged into the
-        hypothesis.  To switch, the engine must be idle; not with an LM attached (LasrError, LASR_ESTATE).  beam = 1: LasrError
-        (LASR_EINVAL)."""
-        self._chk(self.lib.lasr_set_beam_merge(self.ctx, 1 if on else 0))
+        hypothesis.  To switch, the engine must be idle; not with an LM attached (LasrError, LASR_ESTATE) unless lm=True.  beam = 1:
+        LasrError (LASR_EINVAL).
+        lm=True (with on): LASR_BEAM_MERGE_LM, the mode that also merges under LM shallow fusion -- identities follow the fuser's
+        re-picked tokens, attach_lm is accepted while it is on, and without an LM it is exactly on=True.  A merged score is then a
+        log-sum of products of the JOINT's terms, not log P(tokens | audio): see include/lasr.h."""
+        self._chk(self.lib.lasr_set_beam_merge(self.ctx, (N.LASR_BEAM_MERGE_LM if lm else 1) if on else 0))
 
     def fetch_nbest(self, slot, max_hyps=None, cap=65536):
         """fetch(slot) for the whole beam -> [(tokens, frames, logps, score)], best first (score descending, then hypothesis slot

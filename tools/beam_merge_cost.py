@@ -6,7 +6,12 @@ audio from the same state.  Per setting: audio seconds per second (median and ra
 step (lasr_get_stats decode_iters).
     python tools/beam_merge_cost.py            # throughput
     python tools/beam_merge_cost.py timing     # LASR_DBG_TIMING: the selection kernel's own clocks (workgroup 0, synchronous steps),
-                                               # ranking done [3] -> bookkeeping done [4] and entry -> [4], switch off / on, W = 4 and 8"""
+                                               # ranking done [3] -> bookkeeping done [4] and entry -> [4], switch off / on, W = 4 and 8
+    python tools/beam_merge_cost.py lm [W]     # the same throughput comparison with the synthetic LM `lm768` attached:
+                                               # OFF against LASR_BEAM_MERGE_LM, beam W (default 4).  Under a kernel trace
+                                               # (rocprofv3 --kernel-trace --stats -- python tools/beam_merge_cost.py lm) the
+                                               # OFF regions run k_beam_fuse and the ON regions k_beam_fuse_merge: their times
+                                               # stand side by side in the kernel statistics of one job."""
 import ctypes as C
 import json
 import os
@@ -14,6 +19,8 @@ import sys
 import time
 
 timing = "timing" in sys.argv[1:]
+with_lm = "lm" in sys.argv[1:]
+WIDTH = int(sys.argv[sys.argv.index("lm") + 1]) if with_lm and len(sys.argv) > sys.argv.index("lm") + 1 else 4
 if timing:
     os.environ["LASR_DBG_TIMING"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -56,12 +63,14 @@ def phases(W):
 
 def throughput():
     dev = torch.as_tensor(pcm).to("cuda")
-    eng = Engine(sd, cfg, max_streams=B, beam=4, dtype="bf16")
+    eng = Engine(sd, cfg, max_streams=B, beam=WIDTH, dtype="bf16")
+    if with_lm:
+        eng.attach_lm(synth.synth_lm_state_dict("lm768"), int8=False)
     slots = [eng.open() for _ in range(B)]
     res = {"off": [], "on": []}
     for rep in range(10):
         on = bool(rep & 1)
-        eng.set_beam_merge(on)
+        eng.set_beam_merge(on, lm=with_lm)
         for s in slots:
             eng.reset(s, 15)
         iters, steps = 0, 0
@@ -96,4 +105,4 @@ def throughput():
 if timing:
     print(json.dumps({"selection_kernel_clocks": {f"W{W}": phases(W) for W in (4, 8)}}))
 else:
-    print(json.dumps({"model": "cfg2", "dtype": "bf16", "beam": 4, "streams": B, "chunks_per_region": NCH, "throughput": throughput()}))
+    print(json.dumps({"model": "cfg2", "dtype": "bf16", "beam": WIDTH, "lm": "lm768" if with_lm else None, "streams": B, "chunks_per_region": NCH, "throughput": throughput()}))
