@@ -242,7 +242,7 @@ struct lasr_ctx {
     // front-end buffers
     // fused streaming front-end (k_fe_mel + k_ln_tile): nothing is computed on a client chunk that does not complete a model
     // step; the step's launch works through the row's last n_buffer windows, which the PCM ring (ring_chunks =
-    // n_window + n_buffer - 1 chunks) still holds.  pend_serial[s * n_buffer + j] = chunk count of slot s when its
+    // n_window + n_buffer - 1 chunks, at most 16: see FeMelArgs::tp_pk) still holds.  pend_serial[s * n_buffer + j] = chunk count of slot s when its
     // pending frame j was taken; pend_mat = that frame had to be computed early into `pend` (the client pushed more
     // chunks without stepping, the ring was about to lose its window)
     bool fe_fused = false;

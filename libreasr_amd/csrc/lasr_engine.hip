@@ -391,8 +391,11 @@ static int create_impl(lasr_ctx* c, const float* weights, size_t n_weights) {
         c->c_tok_ring = c->c_ntok_end + (size_t)M * lasr_ctx::ENDSLOTS;
     }
     c->h_frames_sub.assign(M, 0); c->h_fetched.assign(M, 0); c->h_cur_seen.assign(M, 0); c->h_avail.assign(M, 0);
-    // (the reference front-end: 10 frames of 128 mels per stacked frame; other shapes take the per-chunk kernels)
-    c->fe_fused = M <= 512 && d.n_buffer <= 4 && d.n_stack == 10 && d.n_mels <= 128 && d.feat == 1280 && !getenv("LASR_FE_LEGACY");
+    // (the reference front-end: 10 frames of 128 mels per stacked frame; other shapes take the per-chunk kernels.  So does a window of
+    //  so many chunks that the fused kernels' ring of n_window + n_buffer - 1 chunks would have more than 16 slots: the ring position
+    //  travels in four bits of FeMelArgs::tp_pk)
+    c->fe_fused = M <= 512 && d.n_buffer <= 4 && d.n_stack == 10 && d.n_mels <= 128 && d.feat == 1280 && d.n_window + d.n_buffer - 1 <= 16
+                  && !getenv("LASR_FE_LEGACY");
     c->h_ring_pos.assign(M, 0);
     c->ring_chunks = c->fe_fused ? d.n_window + d.n_buffer - 1 : d.n_window;
     c->pend_serial.assign((size_t)M * d.n_buffer, 0); c->pend_mat.assign((size_t)M * d.n_buffer, 0);

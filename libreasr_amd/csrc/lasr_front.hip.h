@@ -356,7 +356,7 @@ int lasr_front_create(lasr_ctx* c, int depth, int reset_steps, lasr_front** out)
     if (!c || !out) return LASR_EINVAL;
     *out = nullptr;
     if (c->W > 1) return fail(c, LASR_ESTATE, "lasr_front: greedy decode only (beam %d)", c->W);
-    if (!c->fe_fused) return fail(c, LASR_ESTATE, "lasr_front: needs the fused streaming front-end (<= 512 streams, the reference's frame geometry)");
+    if (!c->fe_fused) return fail(c, LASR_ESTATE, "lasr_front: needs the fused streaming front-end (<= 512 streams, the reference's frame geometry, n_window + n_buffer - 1 <= 16 chunks)");
     lasr_front* f = new lasr_front();
     f->c = c;
     f->depth = std::max(1, std::min(depth > 0 ? depth : 12, lasr_max_inflight(c)));

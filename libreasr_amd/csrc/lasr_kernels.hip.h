@@ -1776,7 +1776,8 @@ struct FeMelArgs {
     const float* src2;       // deferred append of the PREVIOUS chunk of the same rows (else nullptr): the chunk of the last lasr_push_submit
                              // that completed no model step was not appended by a launch of its own -- this launch appends both (src2 first)
     short idx[512];          // -1: the row is not pushed by this launch
-    unsigned char tp_pk[512];    // frames of this step (low nibble) | ring position BEFORE this launch's append (high nibble)
+    unsigned char tp_pk[512];    // frames of this step (low nibble) | ring position BEFORE this launch's append (high nibble: positions
+                                 // 0 .. 15, so ring_chunks <= 16 -- lasr_create keeps longer rings on the per-chunk kernels)
     unsigned short age_pk[512];  // 4 bits per t': chunks pushed since the window of stacked frame t' was current; 15: already in pend
 };
 template <int NSTACK>
