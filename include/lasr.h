@@ -493,6 +493,47 @@ int lasr_score_feats(lasr_ctx* c, const int* slots, int n, const float* feats, c
 int lasr_lm_score(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, const int32_t* n_tokens, int start, double* total,
                   float* logps);
 
+/* ---- Contextual biasing (hotwords): greedy decode prefers the phrases of a list, through a phrase automaton.
+ * Phrases: k >= 1 token lists of length >= 1 (concatenated in `tokens`, n_tokens[j] ids each), every id in [0, vocab) and not blank,
+ * each with a weight weights[j], finite and >= 0, in log-prob units.
+ * Trie: lasr_prefix_tree's nodes and order (node 0 = the root).  w(v), v >= 1: the largest weights[j] over the phrases that have node
+ * v's prefix as a prefix.  Automaton: the Aho-Corasick DFA of the trie -- delta(v, a) is the node of the LONGEST suffix of path(v) . a
+ * that is a trie prefix, 0 if there is none.  The edge list of node v holds every token a with delta(v, a) != 0, ascending in a, as
+ * (tok, next = delta(v, a), bonus = w(next)); a token that is not listed has bonus 0 and leads to the root; blank is never listed.
+ * Storage is CSR: edge_off[n_nodes + 1], edge_tok / edge_next / edge_bonus [n_edges].
+ * The biased decision of a row in node v on the f32 logits z[0..V) of one joint evaluation: s(j) = z[j] + bonus(v, j) (one f32
+ * addition, rounded to nearest) for the tokens listed at v, s(j) = z[j] otherwise; the row takes the first maximum of s (NaN counts as
+ * the maximum, the lowest id wins among equals).  Blank: the frame is done and the node stays.  Any other token is emitted and the row
+ * moves to delta(v, token).  The term that goes into neg_logp and the alignment records is the joint's log-softmax AT THE CHOSEN token,
+ * (z[chosen] - max z) - log sum exp(z - max z): the bonus steers the choice and is not part of any reported score.  Frame cursor,
+ * per-frame symbol cap and alignment score are untouched.  A graph whose bonuses are all 0 decodes bit for bit as no graph does.
+ * Non-finite logits: the token is in [0, vocab), the node in [0, n_nodes), other rows are untouched; nothing else is promised.
+ * Not served (each is refused, see below): beam contexts; the combination with an attached LM; per-slot phrase lists (the graph is
+ * context-wide); negative weights; cancelling the bonus of a partial match that fails (greedy decode keeps no score to cancel it from).
+ *
+ * lasr_bias_compile: phrases -> graph.  No context, no GPU, integer arithmetic and max only.  *n_nodes / *n_edges are always set (0 on
+ * LASR_EINVAL).  LASR_EFULL: cap_nodes / cap_edges too small -- nothing else is written, the counts say what is needed.  LASR_EINVAL: a
+ * null argument (depth, the trie depth per node, is optional), k < 1, an empty phrase, an id out of range or equal to blank, a weight
+ * that is negative or not finite, more than 65536 nodes or 2^22 edges. */
+int lasr_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
+                      int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_bonus, int32_t* depth,
+                      int* n_nodes, int* n_edges);
+/* Attach a graph (HOST arrays; copied) to the context: every slot is biased by it and restarts at node 0.  n_nodes == 0 turns biasing
+ * off and frees the tables.  The graph is checked before anything changes -- LASR_EINVAL, nothing changed: n_nodes outside [1, 65536];
+ * edge_off[0] != 0 or decreasing offsets; a node's tokens not ascending, outside [0, vocab) or blank; next outside [1, n_nodes); a bonus
+ * negative or not finite; beam > 1.  LASR_ESTATE, nothing changed: an LM is attached (lasr_attach_lm / lasr_attach_lm_int8 in turn return
+ * LASR_ESTATE while a graph is set: the fuser re-picks on standardised scores, in which a bonus in log-prob units has no defined
+ * place); a submitted step is uncollected or a slot holds an unfetched result (like the record switches the change needs an idle
+ * context, and may happen in mid-stream).  With a graph attached decode evaluates one frame per iteration on every protocol.
+ * A row's node is 0 at lasr_stream_open, after every predictor reset (lasr_stream_reset bit 2, lasr_stream_reset_many, the native
+ * front's reset rule), at the start of every lasr_transcribe_* utterance, after the lattice, score and lm-score calls (which leave
+ * slots as reset 1 | 2 | 4 does) and after lasr_set_bias; reset bits 1, 4 and 8 alone leave it; it is carried across model steps
+ * in both streaming protocols like the predictor state. */
+int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next,
+                  const float* edge_bonus);
+/* The current node of n open slots into nodes (HOST); synchronises.  LASR_ESTATE: biasing is off; a submitted step is uncollected. */
+int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */
@@ -510,6 +551,10 @@ int lasr_predictor(lasr_ctx* c, const int32_t* tok, int B, int U, float* out);
  * logp_max [B], argmax [B] (device). */
 int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, float* logits,
                float* logp_max, int32_t* argmax);
+/* One biased decision per row (see lasr_set_bias) on caller-supplied logits [B, vocab] (device) with the attached graph, row r in
+ * node[r] (HOST, in [0, n_nodes)): tok, next (the node after the decision; node[r] itself on blank) and logp (the term of the
+ * decision), HOST memory, filled before the call returns.  B <= max_streams.  Touches no slot's state.  LASR_ESTATE: biasing is off. */
+int lasr_bias_pick(lasr_ctx* c, const float* logits, const int32_t* node, int B, int32_t* tok, int32_t* next, float* logp);
 
 /* The lattice dynamic programme alone (see lasr_align_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
  * [T_i][U_i + 1] f32, concatenated (column U_i of emit_lp is not read); T, U: HOST int32 [n] (T >= 1, 0 <= U <= 1535).  Results in HOST

@@ -91,6 +91,11 @@ SYMBOLS = [
     ("lasr_score_feats", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_lattice_tree_dp", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, _P, _P]),
     ("lasr_lm_score", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, _P]),
+    ("lasr_bias_compile", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
+                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("lasr_set_bias", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    ("lasr_bias_state", C.c_int, [_P, _P, C.c_int, _P]),
+    ("lasr_bias_pick", C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
     ("lasr_logmel", C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     ("lasr_stack", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     ("lasr_encoder", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -134,6 +134,32 @@ class LibreASR:
             transcript = self.lang.numericalize(transcript)
         return [int(t) for t in transcript]
 
+    def set_hotwords(self, phrases, boost=2.0):
+        """Contextual biasing: greedy decode (transcribe and stream alike) prefers the listed phrases from now on.  phrases: lists
+        of non-blank token ids, or text when the language object can numericalize (the rule `align` uses); boost: one float, or
+        one per phrase -- finite, >= 0, in log-prob units, added to the joint's logit of a token that continues a phrase (the
+        largest boost among the phrases that share the matched prefix).  None or [] clears.  The default 2.0 is a PLACEHOLDER for a
+        knob nobody has tuned on real data: choose a value on held-out audio.  The bonus steers the choice only; reported
+        confidences and scores stay the joint's.  Raises ValueError on a beam engine (a hypothesis slot would have to carry its
+        automaton node through the beam's parent indirection and merging would have to include it in the identity) and with an LM
+        attached (the fuser re-picks on standardised scores, in which a bonus in log-prob units has no defined place)."""
+        if phrases is None or len(phrases) == 0:
+            self.engine.set_bias(None)
+            return
+        if self.engine.beam > 1:
+            raise ValueError("set_hotwords needs greedy decode (beam = 1): a hypothesis slot would have to carry its automaton node "
+                             "through the beam's parent indirection")
+        if self.engine.lm_cfg is not None:
+            raise ValueError("set_hotwords refuses an attached LM: the fuser re-picks on standardised scores, in which a bonus in "
+                             "log-prob units has no defined place")
+        ids = [self._ids(p) for p in phrases]
+        w = [float(boost)] * len(ids) if np.ndim(boost) == 0 else [float(b) for b in boost]
+        if len(w) != len(ids):
+            raise ValueError("boost: one float, or one per phrase")
+        if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
+            raise ValueError("set_hotwords: phrases of at least one token, boosts finite and >= 0")
+        self.engine.set_bias(self.engine.bias_compile(ids, w))
+
     def _posteriors(self, r):
         """per token of an align_pcm(posteriors=True) or align_band_post_pcm result: the lattice's view of where the token is, over all
         alignments (of a band: over those inside its windows; occ_emit is then in band layout, column u - lo[frame]).  Both

@@ -307,6 +307,12 @@ struct lasr_ctx {
     std::vector<long long> slot_frames;   // encoder frames the slot has consumed since lasr_stream_open (either protocol)
     int* align_host = nullptr;            // pinned [frames M x TOKRING][log p M x TOKRING]: k_select's record rings (allocated on first use)
     int* c_frame_ring = nullptr; float* c_logp_ring = nullptr;      // device views of the two halves
+    // contextual biasing (lasr_set_bias): the attached graph, one device block [off | tok | next | bonus] (DecState's
+    // bias_* point into it; ds.bias_node != nullptr is "on"), the per-row nodes, and lasr_bias_pick's node row (both kept once allocated)
+    int bias_nodes = 0;
+    int* bias_tab = nullptr;
+    int* bias_node_dev = nullptr;         // [M]
+    int* bias_pick_dev = nullptr;         // [M]
 
     // in-job timing of the dominant kernel (lasr_cell_prof): one HIP-event pair around the encoder-cell sequence of
     // every model step, on the stream the cells are launched on; harvested lazily (ring of pairs)

@@ -24,6 +24,7 @@ int apply_reset(lasr_ctx* c, const DecView& v, bool any_pred, int mask = 3, bool
         a.pred_h0[l] = c->pred[l].h0; a.pred_c0[l] = c->pred[l].c0;
     }
     a.token = c->ds.token; a.emit = c->ds.emit;
+    a.bias_node = c->ds.bias_node;           // (null unless a graph is attached: greedy contexts only)
     const bool use_bos = c->bos_ready && !beam && !plain_rows && c->W == 1 && (mask & 2);
     if (use_bos) {
         for (int l = 0; l < a.Lp; ++l) { a.bos_h[l] = c->bos_h[l]; a.bos_c[l] = c->d.pred_cell ? c->bos_c[l] : nullptr; }

@@ -22,6 +22,7 @@ static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStrea
 #include "lasr_lattice.hip.h"
 #include "lasr_lattice_post.hip.h"
 #include "lasr_prefix_tree.hip.h"
+#include "lasr_bias.hip.h"
 #include "lasr_lattice_tree.hip.h"
 #include "lasr_lm_score.hip.h"
 #include "lasr_weights.hip.h"
@@ -2134,6 +2135,76 @@ int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* token
     return fetch_many(c, slots, n, tokens, frames, logps, cap, n_new);
 }
 
+// ---------------------------------------------------------------------------- contextual biasing
+int lasr_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
+                      int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_bonus, int32_t* depth,
+                      int* n_nodes, int* n_edges) {
+    return lasr_bias::compile(tokens, n_tokens, weights, k, vocab, blank, cap_nodes, cap_edges, edge_off, edge_tok, edge_next, edge_bonus,
+                              depth, n_nodes, n_edges);
+}
+// Greedy decode: with a graph attached the decode launches run k_select<.., BIAS = true> at one frame per iteration, and every
+// row carries its automaton node beside its predictor state (DecState::bias_node; null = off, the default).  Like the record
+// switches this changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  The
+// graph is checked on the host before anything changes.
+int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_bonus) {
+    if (!c) return LASR_EINVAL;
+    if (c->W > 1)
+        return fail(c, LASR_EINVAL, "contextual biasing serves greedy decode (beam = 1): a hypothesis slot would have to carry its node through "
+                                    "the parent indirection and merging would have to include it in the identity");
+    if (n_nodes == 0 && !c->ds.bias_node) return LASR_OK;       // (off already: also fine while steps are in flight)
+    if (n_nodes != 0) {
+        if (c->lm.on)
+            return fail(c, LASR_ESTATE, "lasr_set_bias refuses an attached LM (the fuser re-picks on standardised scores, in which a bonus in "
+                                        "log-prob units has no defined place)");
+        const char* bad = lasr_bias::validate(n_nodes, edge_off, edge_tok, edge_next, edge_bonus, c->d.vocab, c->d.blank);
+        if (bad) return fail(c, LASR_EINVAL, "lasr_set_bias: %s", bad);
+    }
+    RC(toggle_prologue(c, "slot %d has %d unfetched token(s): fetch them before the switch"));
+    int* tab = nullptr;
+    size_t E = 0;
+    if (n_nodes) {
+        E = (size_t)edge_off[n_nodes];
+        std::vector<int> img((size_t)n_nodes + 1 + 3 * E);
+        std::copy(edge_off, edge_off + n_nodes + 1, img.begin());
+        if (E) {
+            std::copy(edge_tok, edge_tok + E, img.begin() + n_nodes + 1);
+            std::copy(edge_next, edge_next + E, img.begin() + n_nodes + 1 + E);
+            memcpy(img.data() + n_nodes + 1 + 2 * E, edge_bonus, sizeof(float) * E);
+        }
+        RC(upload(c, &tab, (const int*)img.data(), img.size()));
+        if (!c->bias_node_dev) RC(dalloc(c, &c->bias_node_dev, (size_t)c->M));
+        HIPCHK(c, hipMemset(c->bias_node_dev, 0, sizeof(int) * (size_t)c->M));      // every slot starts over at the root
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    dfree(c, c->bias_tab);
+    c->bias_tab = tab;
+    c->bias_nodes = n_nodes;
+    DecState& s = c->ds;
+    s.bias_node = n_nodes ? c->bias_node_dev : nullptr;
+    s.bias_off = tab;
+    s.bias_tok = tab ? tab + n_nodes + 1 : nullptr;
+    s.bias_next = tab ? tab + n_nodes + 1 + E : nullptr;
+    s.bias_bonus = tab ? (const float*)(tab + n_nodes + 1 + 2 * E) : nullptr;
+    return LASR_OK;
+}
+
+int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes) {
+    if (!c) return LASR_EINVAL;
+    if (!c->ds.bias_node) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    RC(check_slots(c, slots, n, true));
+    if (n == 0) return LASR_OK;
+    if (!nodes) return fail(c, LASR_EINVAL, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    std::vector<int> all((size_t)c->M);
+    HIPCHK(c, hipMemcpy(all.data(), c->bias_node_dev, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) nodes[i] = all[slots[i]];
+    return LASR_OK;
+}
+
 // ---------------------------------------------------------------------------- beam: per-token records and the whole beam
 // k_beam_select_rw<WT, true> stores, beside the trellis word of every slot it extends by a non-blank token, the frame cursor and the
 // f32 term it added to the parent's score (BeamState::rec; null = off, the default: the <WT, false> instantiation).  Toggling
@@ -2335,9 +2406,33 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
     launch_logits(c, v, logits, B, false);
     if (logp_max && argmax) {
         DecState s = c->ds;
+        s.bias_node = nullptr;                       // the joint's own argmax, whatever graph is attached (lasr_bias_pick is the biased one)
         launch_select<true>(c->stream, B, logits, V, c->d.blank, 1, nullptr, s, 0, logp_max, argmax, 1, c->M);
     }
     HIPCHK(c, hipGetLastError());
+    return LASR_OK;
+}
+
+// one biased decision per row on the caller's logits with the attached graph: k_select<PLAIN, 1, KEEP, BIAS> on a node row of
+// its own -- no slot's state is read or written
+int lasr_bias_pick(lasr_ctx* c, const float* logits, const int32_t* node, int B, int32_t* tok, int32_t* next, float* logp) {
+    if (!c || !logits || !node || !tok || !next || !logp || B < 1 || B > c->d.max_streams) return c ? fail(c, LASR_EINVAL, "bad argument") : LASR_EINVAL;
+    if (!c->ds.bias_node) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
+    for (int r = 0; r < B; ++r)
+        if (node[r] < 0 || node[r] >= c->bias_nodes) return fail(c, LASR_EINVAL, "row %d: node %d outside [0, %d)", r, node[r], c->bias_nodes);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t M = (size_t)c->M;
+    if (!c->bias_pick_dev) RC(dalloc(c, &c->bias_pick_dev, 3 * M));      // [node -> next | tok | log p]
+    int* nd = c->bias_pick_dev;
+    HIPCHK(c, hipMemcpyAsync(nd, node, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    DecState s = c->ds;
+    s.bias_node = nd;
+    launch_select<true>(c->stream, B, logits, c->d.vocab, c->d.blank, 1, nullptr, s, 0, (float*)(nd + 2 * M), nd + M, 1, c->M);
+    HIPCHK(c, hipGetLastError());
+    std::vector<int> out(3 * M);
+    HIPCHK(c, hipMemcpyAsync(out.data(), nd, sizeof(int) * 3 * M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int r = 0; r < B; ++r) { next[r] = out[r]; tok[r] = out[M + r]; memcpy(&logp[r], &out[2 * M + r], sizeof(float)); }
     return LASR_OK;
 }
 
@@ -2517,6 +2612,9 @@ static int lm_side_setup(lasr_ctx* c) {
 static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights, bool q8) {
     if (!c) return LASR_EINVAL;
     if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
+    if (c->ds.bias_node)
+        return fail(c, LASR_ESTATE, "a bias graph is set (the fuser re-picks on standardised scores, in which a bonus in log-prob units has "
+                                    "no defined place): lasr_set_bias(c, 0, ...) first");
     if (c->beam_merge == 1) return fail(c, LASR_ESTATE, "beam merging is on in the mode that refuses an LM (lasr_set_beam_merge(c, 0) or (c, LASR_BEAM_MERGE_LM) first)");
     if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)

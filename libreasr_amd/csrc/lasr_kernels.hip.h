@@ -174,6 +174,7 @@ struct ResetArgs {
     const float* pred_c0[8];
     int* token;
     int* emit;
+    int* bias_node;           // contextual biasing: the row's automaton node restarts with the predictor (null: off)
     // greedy decode: the predictor state AFTER its BOS step and the joint's predictor half for it (models.py:489) are constants of
     // the model -- captured once at lasr_create (k_bos_capture) and stored here instead of running the predictor on BOS per reset
     const float* bos_h[8];    // [H] per layer (null: the caller runs the BOS pass)
@@ -208,6 +209,7 @@ inline __global__ void k_reset_rows(const ResetArgs a) {
     if (u == 0 && (a.mask & 2)) {
         a.emit[rp] = ((wh & 2) && !bos) ? 1 : 0;
         if (wh & 2) a.token[rp] = a.bos;
+        if ((wh & 2) && a.bias_node) a.bias_node[rp] = 0;
         if (W > 1)
             for (int b = 0; b < W; ++b) {
                 a.parent[rp + b] = b;
@@ -302,6 +304,13 @@ struct DecState : ContRound {
     const int* lm_valid; // [M] the LM has advanced at least once since the last LM reset
     float lm_alpha, lm_theta, lm_min;
     unsigned long long* dbg;   // LASR_DBG_TIMING: phase stamps of k_select's workgroup 0 (wall clock, 10 ns ticks)
+    // contextual biasing (lasr_set_bias): the row's node in the phrase automaton and the automaton's edge lists (CSR
+    // over the nodes, tokens ascending per node).  bias_node == nullptr: off -- the launcher then picks the BIAS = false kernels
+    int* bias_node;            // [M]
+    const int* bias_off;       // [n_nodes + 1]
+    const int* bias_tok;       // [n_edges]
+    const int* bias_next;      // [n_edges] in [1, n_nodes)
+    const float* bias_bonus;   // [n_edges] finite, >= 0
 };
 
 // block-wide sum over 256 threads (4 waves); every thread gets the result
@@ -563,13 +572,19 @@ __device__ __forceinline__ int lm_fused_argmax(const float (&z)[KEEP], float den
 // barrier in the state machine).  Same decisions, same order, same arithmetic per frame as the one-frame loop.
 // KEEP: logits kept in registers per thread and frame (8 covers V <= 2048, 16 V <= 4096; the rest of a larger row is re-read).  A
 // slot past V holds -inf and contributes an exact zero, so the results do not depend on KEEP.
-template <bool PLAIN, int LAT, int KEEP>
+// BIAS: contextual biasing -- the decision is re-picked among (z[arg], arg) and the edges of the row's automaton node,
+// and the row's node follows the emitted token.  One frame per launch (LAT = 1), as the LM re-pick first ran; BIAS = false is the
+// kernel as it was, instruction for instruction (the block below is `if constexpr`).
+template <bool PLAIN, int LAT, int KEEP, bool BIAS = false>
 __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits, int V, int blank, int max_iters,
                                                 const int* __restrict__ T_row, DecState s, int iter_slot_in,
                                                 float* __restrict__ out_logp, int* __restrict__ out_arg, int la, int M) {
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    static_assert(!BIAS || LAT == 1, "biasing decides one frame per launch");
     const bool dbgt = !PLAIN && s.dbg && r == 0 && tid == 0;
     const unsigned long long t_entry = dbgt ? wall_clock64() : 0ull;
+    int bias_v = 0;                                               // the row's automaton node (in flight with the logits)
+    if constexpr (BIAS) bias_v = s.bias_node[r];
     float zv[LAT][KEEP];
 #pragma unroll
     for (int k = 0; k < LAT; ++k) {
@@ -649,8 +664,51 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
         sums[k] = sum;
         logp[k] = -logf(sum);                // log_softmax at the argmax = z_max - logsumexp
     }
+    int node_next = 0;
+    if constexpr (BIAS) {
+        // ---- the biased decision: s(j) = z[j] + bonus(v, j) on the edges of the row's node v, s(j) = z[j] elsewhere;
+        // the first maximum of s under amax_before.  Bonuses are >= 0 and arg is the first maximum of z, so the winner is the best
+        // of (z[arg], arg) and the listed edges: the workgroup strides over deg(v) edges, never over V again.  The edge tokens of a
+        // node are distinct, so (s, tok) identifies its edge and the reduction need not carry it: the thread that scanned the
+        // winning edge knows.  The same scan notes the edge of arg itself (where the row goes if the unbiased choice stands).
+        const int e0 = s.bias_off[bias_v], e1 = s.bias_off[bias_v + 1];
+        const float* z = logits + (size_t)r * V;
+        float eb = -INFINITY, my_z = 0.f;
+        int ea = 0x7fffffff, my_next = 0, arg_next = 0;
+        for (int e = e0 + tid; e < e1; e += 256) {
+            const int tk = s.bias_tok[e];
+            const float zt = z[tk];                  // (the row this workgroup has just streamed)
+            const float sc = __fadd_rn(zt, s.bias_bonus[e]);
+            const int nx = s.bias_next[e];
+            if (tk == arg[0]) arg_next = nx;
+            if (amax_before(sc, tk, eb, ea)) { eb = sc; ea = tk; my_z = zt; my_next = nx; }
+        }
+        const int my_tok = ea;
+        wave_argmax_f32(eb, ea);
+        __shared__ float bz;
+        __shared__ int bn;
+        if (lane == 0) { sv[0][w] = eb; si[0][w] = ea; }      // (every thread is past its reads of sv / si: the barrier behind ss)
+        if (tid == 0) { bz = 0.f; bn = 0; }
+        __syncthreads();
+        eb = sv[0][0]; ea = si[0][0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+            if (amax_before(sv[0][q], si[0][q], eb, ea)) { eb = sv[0][q]; ea = si[0][q]; }
+        const bool by_edge = ea != arg[0] && (unsigned)ea < (unsigned)V && amax_before(eb, ea, best[0], arg[0]);
+        if (by_edge) { if (my_tok == ea) { bz = my_z; bn = my_next; } }
+        else if (arg_next) bn = arg_next;            // (targets are >= 1: 0 = arg is not listed)
+        __syncthreads();
+        if (by_edge) {
+            arg[0] = ea;
+            logp[0] = (bz - best[0]) - logf(sums[0]);            // log-softmax at the chosen token (arg itself: today's bits)
+        }
+        node_next = arg[0] != blank ? bn : bias_v;                // a blank decision leaves the node; an unlisted token leads to the root
+    }
     if (PLAIN) {
-        if (tid == 0) { out_logp[r] = logp[0]; out_arg[r] = arg[0]; }
+        if (tid == 0) {
+            out_logp[r] = logp[0]; out_arg[r] = arg[0];
+            if constexpr (BIAS) s.bias_node[r] = node_next;
+        }
         return;
     }
     if (dbgt) s.dbg[2] = wall_clock64();                          // statistics of all frames done
@@ -708,6 +766,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
                 }
                 n0 += 1;
                 s.token[r] = tok;
+                if constexpr (BIAS) s.bias_node[r] = node_next;      // beside the token: the same release orders both
             }
             frame_done = it >= max_iters;           // per-frame symbol cap
         }

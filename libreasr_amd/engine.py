@@ -27,6 +27,44 @@ def _ptr(x):
     raise TypeError(type(x))
 
 
+class BiasGraph:
+    """The phrase automaton of contextual biasing in lasr_set_bias' layout (CSR edge lists, int32 / float32 host arrays);
+    depth: the trie depth per node."""
+
+    def __init__(self, edge_off, edge_tok, edge_next, edge_bonus, depth=None):
+        self.edge_off = np.ascontiguousarray(edge_off, dtype=np.int32)
+        self.edge_tok = np.ascontiguousarray(edge_tok, dtype=np.int32)
+        self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32)
+        self.edge_bonus = np.ascontiguousarray(edge_bonus, dtype=np.float32)
+        self.depth = None if depth is None else np.ascontiguousarray(depth, dtype=np.int32)
+        self.n_nodes = int(self.edge_off.size) - 1
+        self.n_edges = int(self.edge_tok.size)
+
+
+def bias_compile(lib, phrases, weights, vocab, blank):
+    """lasr_bias_compile (no context, no GPU): sized by a first call with no room, filled by the second"""
+    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+    k = len(toks)
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if k < 1 or w.size != k:
+        raise ValueError("bias_compile: at least one phrase and one weight per phrase")
+    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
+    nn, ne = C.c_int(0), C.c_int(0)
+    one = [np.zeros(1, np.int32) for _ in range(3)] + [np.zeros(1, np.float32)]
+    rc = lib.lasr_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), 0, 0, _ptr(one[0]), _ptr(one[1]), _ptr(one[2]),
+                               _ptr(one[3]), None, C.byref(nn), C.byref(ne))
+    if rc != N.LASR_EFULL:
+        raise N.LasrError(rc, "lasr_bias_compile: phrases of >= 1 ids in [0, vocab) other than blank, weights finite and >= 0")
+    off, dep = np.zeros(nn.value + 1, np.int32), np.zeros(nn.value, np.int32)
+    etok, enxt, ebon = np.zeros(max(ne.value, 1), np.int32), np.zeros(max(ne.value, 1), np.int32), np.zeros(max(ne.value, 1), np.float32)
+    rc = lib.lasr_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), nn.value, ne.value, _ptr(off), _ptr(etok),
+                               _ptr(enxt), _ptr(ebon), _ptr(dep), C.byref(nn), C.byref(ne))
+    if rc != 0:
+        raise N.LasrError(rc, "lasr_bias_compile")
+    return BiasGraph(off, etok[:ne.value], enxt[:ne.value], ebon[:ne.value], dep)
+
+
 class Engine:
     def __init__(self, state_dict, cfg=None, max_streams=64, device=0, max_iters_offline=3,
                  max_iters_stream=10, blank=0, bos=2, dtype="f32", beam=1, **frontend):
@@ -707,6 +745,40 @@ class Engine:
         if rc != 0:
             raise N.LasrError(rc, "lasr_prefix_tree: bad candidate list")
         return {"parent": par[:n.value].copy(), "label": lab[:n.value].copy(), "depth": dep[:n.value].copy(), "term": term[:k].copy()}
+
+    # ------------------------------------------------------------------ contextual biasing (hotwords)
+    def bias_compile(self, phrases, weights):
+        """Phrases (token-id lists) and one weight each (log-prob units, finite, >= 0) -> BiasGraph, the phrase automaton of
+        lasr_bias_compile (host only; include/lasr.h has the definition)."""
+        return bias_compile(self.lib, phrases, weights, self.desc.vocab, self.desc.blank)
+
+    def set_bias(self, graph):
+        """Attach a BiasGraph to the context (every slot is biased and restarts at the root); None turns biasing off.  Needs
+        an idle context and greedy decode without an LM (lasr_set_bias)."""
+        if graph is None:
+            self._chk(self.lib.lasr_set_bias(self.ctx, 0, None, None, None, None))
+            return
+        self._chk(self.lib.lasr_set_bias(self.ctx, int(graph.n_nodes), _ptr(graph.edge_off), _ptr(graph.edge_tok),
+                                         _ptr(graph.edge_next), _ptr(graph.edge_bonus)))
+
+    def bias_state(self, slots):
+        """-> int32 [n]: the automaton node of every listed slot (synchronises)"""
+        a, p, n = self._slots(slots)
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self.lib.lasr_bias_state(self.ctx, p, n, _ptr(out)))
+        return out[:n]
+
+    def bias_pick(self, logits, nodes):
+        """One biased decision per row: logits [B, vocab] (device f32), nodes [B] -> (tok int32 [B], next int32 [B], logp
+        float32 [B]) on the host (lasr_bias_pick; no slot's state is touched)."""
+        logits = logits.contiguous()
+        B = int(logits.shape[0])
+        nd = np.ascontiguousarray(np.asarray(nodes, dtype=np.int32).reshape(-1))
+        if nd.size != B or logits.shape[1] != self.desc.vocab or logits.dtype != torch.float32:
+            raise ValueError("bias_pick: logits [B, vocab] float32 and one node per row")
+        tok, nxt, lp = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
+        self._chk(self.lib.lasr_bias_pick(self.ctx, _ptr(logits), _ptr(nd), B, _ptr(tok), _ptr(nxt), _ptr(lp)))
+        return tok, nxt, lp
 
     def _cat_pcm(self, pcm_list):
         """-> (all utterances concatenated: one device tensor if every one is, else one host array; int64 sample counts)"""
