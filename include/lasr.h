@@ -508,8 +508,9 @@ int lasr_lm_score(lasr_ctx* c, const int* slots, int n, const int32_t* tokens, c
  * (z[chosen] - max z) - log sum exp(z - max z): the bonus steers the choice and is not part of any reported score.  Frame cursor,
  * per-frame symbol cap and alignment score are untouched.  A graph whose bonuses are all 0 decodes bit for bit as no graph does.
  * Non-finite logits: the token is in [0, vocab), the node in [0, n_nodes), other rows are untouched; nothing else is promised.
- * Not served (each is refused, see below): beam contexts; the combination with an attached LM; per-slot phrase lists (the graph is
- * context-wide); negative weights; cancelling the bonus of a partial match that fails (greedy decode keeps no score to cancel it from).
+ * Not served here: beam contexts (refused: they have lasr_set_beam_bias, below, where the bonus is part of the ranking score and a
+ * partial match that fails hands it back -- greedy decode keeps no score to cancel it from); the combination with an attached LM
+ * (refused); per-slot phrase lists (the graph is context-wide); negative weights (refused).
  *
  * lasr_bias_compile: phrases -> graph.  No context, no GPU, integer arithmetic and max only.  *n_nodes / *n_edges are always set (0 on
  * LASR_EINVAL).  LASR_EFULL: cap_nodes / cap_edges too small -- nothing else is written, the counts say what is needed.  LASR_EINVAL: a
@@ -534,6 +535,63 @@ int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32
 /* The current node of n open slots into nodes (HOST); synchronises.  LASR_ESTATE: biasing is off; a submitted step is uncollected. */
 int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes);
 
+/* ---- Contextual biasing in beam search: the bonus is part of the ranking score and is revoked when a match fails.
+ * The graph in beam form.  Phrases, weights (finite, >= 0), trie nodes and order, w(v) and delta(v, a) are lasr_bias_compile's.  Per
+ * node also: term(v) -- some phrase ends exactly at v; cum(0) = 0, cum(v) = cum(parent v) + w(v); held(0) = 0, held(v) = 0 if term(v),
+ * else held(parent v) + w(v): the part of the bonus collected so far that is still revocable.  For a node v, a non-blank token a and
+ * n = delta(v, a): gain(v, a) = w(n) if n is v's trie child by a; otherwise (a failure transition, n = 0 included) gain(v, a) =
+ * cum(n) - held(v).  Node v's edge list holds every a with delta(v, a) != 0, ascending, as (tok, next, gain); back[v] = -held(v) is the
+ * gain of every non-blank token that is NOT listed (it leads to the root).  Blank has gain 0 and the node stays.  Sums are taken in
+ * double in path order; every gain and back is rounded once to f32.  The summed gains of any token string from the root equal the
+ * bonus of its completed matches plus held(current node).  Stated limits: a token shared by a completed phrase and an overlapping
+ * next match is credited in both; a phrase that completes only as a proper suffix of a longer partial match that then fails is not
+ * credited; at the end of audio an unfinished match keeps its held bonus (the caller reads it as -back[node]).
+ * Storage: lasr_bias_compile's CSR arrays with edge_gain [n_edges] (either sign) and node_back [n_nodes] (<= 0, node_back[0] = 0).
+ *
+ * The biased round is the beam's selection round (one per decode iteration and stream: the slots that are done with the frame are
+ * carried, every other live slot offers extensions, the W best candidates survive in the order score descending, source slot
+ * ascending, carried first, token id ascending) with three changes.  (1) A slot at node v with the joint's log-probs lp[0..V) forms
+ * s(j) = lp[j] + g(v, j) (one f32 addition, rounded to nearest), g = gain for listed tokens, back[v] for other non-blank tokens, 0
+ * for blank, and offers its W best tokens by s, descending, the lower id first among equals.  (2) A candidate's score is
+ * (score + (double)lp[j]) + (double)g(v, j), the additions in that order.  (3) A survivor extended by a non-blank token j takes node
+ * delta(v, j), v its PARENT's node; a blank extension and a carried slot keep the parent's node; a dead slot's node is 0.
+ * The per-token record (lasr_set_beam_records) stays the joint's lp[j] without the gain; scores[] of lasr_fetch_nbest and neg_logp
+ * are the ranking scores, gains included (lasr_bias_walk gives the gains of a token list back).  A graph whose gains and backs are
+ * all 0 decodes bit for bit as no graph does.  Non-finite logits: tokens stay in [0, V), nodes in [0, n_nodes), other streams are
+ * untouched; nothing else is promised.
+ * Merging (lasr_set_beam_merge 1, or LASR_BEAM_MERGE_LM without an LM) is allowed and the identity is unchanged: equal token lists
+ * since the last predictor reset have equal nodes and equal summed gains -- unless lasr_set_beam_bias was called since that reset; the
+ * kept (lowest) slot's node then wins, as the kept slot's LM state does under LASR_BEAM_MERGE_LM.
+ * Not served: the combination with an attached LM (refused both ways); per-slot phrase lists; negative weights; finalising a held
+ * bonus at the end of audio.
+ *
+ * lasr_beam_bias_compile: phrases -> graph in beam form; lasr_bias_compile's contract (host only; counts always set; LASR_EFULL /
+ * LASR_EINVAL as there), and LASR_EINVAL also if any |gain| or |back| exceeds 1000 (the selection kernel's pruning relies on it). */
+int lasr_beam_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
+                           int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_gain, float* node_back,
+                           int32_t* depth, int* n_nodes, int* n_edges);
+/* Attach a graph in beam form (HOST arrays; copied) to a beam context: every hypothesis slot is biased by it and restarts at node 0;
+ * the slots' scores stay what they are, at switch-on and at switch-off.  n_nodes == 0 turns biasing off and frees the tables.  A
+ * context that never calls this launches the kernels it always launched.  Checked before anything changes -- LASR_EINVAL, nothing
+ * changed: a greedy context (it has lasr_set_bias); lasr_set_bias' graph checks, except that a gain may have either sign; a gain or
+ * back that is not finite or beyond 1000 in magnitude; back > 0; node_back[0] != 0; a null array.  LASR_ESTATE, nothing changed: an
+ * LM is attached (lasr_attach_lm in turn returns LASR_ESTATE while a beam graph is set); a submitted step is uncollected or a slot
+ * holds an unfetched result (the switch needs an idle context, drops the cached decode graphs, and may happen in mid-stream).
+ * A slot's node is 0 at lasr_stream_open, after every predictor reset (bit 2: all W slots of the stream), at the start of every
+ * lasr_transcribe_* utterance and after lasr_set_beam_bias; reset bits 1, 4 and 8 alone leave it; it is carried across model steps on
+ * both streaming protocols. */
+int lasr_set_beam_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next,
+                       const float* edge_gain, const float* node_back);
+/* The nodes of the W hypothesis slots of one open stream, in slot order (HOST, nodes[beam]); -1 for a dead slot; synchronises.
+ * LASR_ESTATE: beam biasing is off; a submitted step is uncollected. */
+int lasr_beam_bias_state(lasr_ctx* c, int slot, int32_t* nodes);
+/* Tokens through a graph in beam form, host only: from node `start`, n tokens (blank: gain 0, the node stays; a token that is not
+ * listed: back[node], to the root) -> *end_node, *total = the double sum of the f32 gains in order, gains[n] (optional; so are the
+ * other two).  score - total is the acoustic score of a hypothesis whose tokens were decoded since a reset.  LASR_EINVAL: a null
+ * table, start outside [0, n_nodes), n < 0, a negative token, an edge target outside [0, n_nodes). */
+int lasr_bias_walk(int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_gain,
+                   const float* node_back, int blank, const int32_t* tokens, int n, int start, int* end_node, double* total, float* gains);
+
 /* ---- op-level entry points (parity tests and roofline micro-benchmarks).  Device pointers
  * unless noted; all enqueue on the ctx stream and return without synchronising. -------------- */
 /* log-mel of whole signals: pcm [B, N] -> logmel [B, T, n_mels], T = 1 + N / hop. */
@@ -555,6 +613,17 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
  * node[r] (HOST, in [0, n_nodes)): tok, next (the node after the decision; node[r] itself on blank) and logp (the term of the
  * decision), HOST memory, filled before the call returns.  B <= max_streams.  Touches no slot's state.  LASR_ESTATE: biasing is off. */
 int lasr_bias_pick(lasr_ctx* c, const float* logits, const int32_t* node, int B, int32_t* tok, int32_t* next, float* logp);
+/* One biased selection round (see lasr_set_beam_bias) of n streams on caller-supplied logits [n * beam, vocab] (device, row = stream *
+ * beam + slot) with the attached graph -- the decode loop's own kernel on a scratch state; no slot's state is read or written.  HOST
+ * inputs per row: score, alive, inB (1: the slot is done with the frame and is carried), node in [0, n_nodes); per stream: rounds, the
+ * selection rounds already done on the frame (the round is at the per-frame cap when rounds + 1 >= max_iters).  HOST outputs per row,
+ * filled before the call returns: parent (slot of the same stream), emit (1: extended by a non-blank token), token (the extension's
+ * token, -1 unless emit), score, alive, inB (all 0 when the stream's frame is finished), node, term (the joint's log p of the
+ * extension, 0 unless emit).  n <= max_streams; needs an idle context.  LASR_ESTATE: beam biasing is off.  LASR_EINVAL: a greedy
+ * context, a null argument, a node out of range, rounds < 0, max_iters < 1. */
+int lasr_beam_bias_round(lasr_ctx* c, const float* logits, int n, const double* score, const int32_t* alive, const int32_t* inB,
+                         const int32_t* node, const int32_t* rounds, int max_iters, int32_t* parent, int32_t* token, int32_t* emit,
+                         double* score_out, int32_t* alive_out, int32_t* inB_out, int32_t* node_out, float* term);
 
 /* The lattice dynamic programme alone (see lasr_align_*), on n caller-supplied lattices: blank_lp / emit_lp host or device, per lattice
  * [T_i][U_i + 1] f32, concatenated (column U_i of emit_lp is not read); T, U: HOST int32 [n] (T >= 1, 0 <= U <= 1535).  Results in HOST

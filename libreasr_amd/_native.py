@@ -96,6 +96,12 @@ SYMBOLS = [
     ("lasr_set_bias", C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     ("lasr_bias_state", C.c_int, [_P, _P, C.c_int, _P]),
     ("lasr_bias_pick", C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
+    ("lasr_beam_bias_compile", C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ("lasr_set_beam_bias", C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    ("lasr_beam_bias_state", C.c_int, [_P, C.c_int, _P]),
+    ("lasr_bias_walk", C.c_int, [C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), _P]),
+    ("lasr_beam_bias_round", C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("lasr_logmel", C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     ("lasr_stack", C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.POINTER(C.c_int)]),
     ("lasr_encoder", C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),

@@ -86,12 +86,18 @@ class LibreASR:
         else:
             self.engine.set_beam_merge(bool(merge))
 
-    def _nbest(self, slot, k):
+    def _nbest(self, slot, k, bonus=False):
         """-> up to k hypotheses, best first: {"score": sum of log p of every decision, "tokens": [(token_id, time_s, confidence)]}.
         With merging on (merge=True, Engine.set_beam_merge) the hypotheses are pairwise distinct and "score" is the log of the SUMMED
         probability of the alignments that were merged into the hypothesis; its times and confidences are those of the best-ranked
-        alignment among them."""
-        return [{"score": sc, "tokens": self._aligned(t, f, lp)} for t, f, lp, sc in self.engine.fetch_nbest(slot, int(k))]
+        alignment among them.
+        bonus=True (offline results with beam hotwords set): "score" is the ranking score, hotword gains included, and "bonus" the
+        summed gain of the hypothesis' tokens from the root (Engine.bias_walk): score - bonus is the acoustic score."""
+        out = [{"score": sc, "tokens": self._aligned(t, f, lp)} for t, f, lp, sc in self.engine.fetch_nbest(slot, int(k))]
+        if bonus:
+            for h in out:
+                h["bonus"] = float(self.engine.bias_walk([t[0] for t in h["tokens"]])[1])
+        return out
 
     def transcribe(self, audio, return_ids=False, return_alignment=False, nbest=None, merge=None):
         """Whole utterance(s): fresh state, greedy, max_iters_offline (Transcribe RPC, api-server.py:64-80).
@@ -100,6 +106,7 @@ class LibreASR:
         a beam engine raises NotImplementedError: use nbest=.
         nbest=k (beam engines; ValueError on a greedy one): per utterance up to k hypotheses of the final beam, best first, each
         {"score": float, "tokens": [(token_id, time_s, confidence)]} with time_s / confidence as above; no merging, no length norm.
+        With set_beam_hotwords in force "score" includes the hotword gains and each hypothesis also carries "bonus", their sum.
         merge=True / False (beam engines; ValueError on a greedy one) turns the merging of hypotheses that hold the same tokens on /
         off and the engine keeps the setting; None leaves it as it is.  See _nbest for what "score" means then.  merge=True raises
         on an engine with an LM attached; merge="lm" merges there too (identities follow the LM fuser's re-picked tokens; a score is
@@ -114,7 +121,7 @@ class LibreASR:
         try:
             self.engine.transcribe_pcm(slots, [self._utterance(a) for a in batch])
             if nbest is not None:
-                out = [self._nbest(s, nbest) for s in slots]
+                out = [self._nbest(s, nbest, bonus=getattr(self.engine, "beam_bias", None) is not None) for s in slots]
             elif return_alignment:
                 out = [self._aligned(*self.engine.fetch_aligned(s)[:3]) for s in slots]
             else:
@@ -140,15 +147,14 @@ class LibreASR:
         one per phrase -- finite, >= 0, in log-prob units, added to the joint's logit of a token that continues a phrase (the
         largest boost among the phrases that share the matched prefix).  None or [] clears.  The default 2.0 is a PLACEHOLDER for a
         knob nobody has tuned on real data: choose a value on held-out audio.  The bonus steers the choice only; reported
-        confidences and scores stay the joint's.  Raises ValueError on a beam engine (a hypothesis slot would have to carry its
-        automaton node through the beam's parent indirection and merging would have to include it in the identity) and with an LM
-        attached (the fuser re-picks on standardised scores, in which a bonus in log-prob units has no defined place)."""
+        confidences and scores stay the joint's.  Raises ValueError on a beam engine (it has set_beam_hotwords, where the bonus
+        is part of the ranking score and a partial match that fails hands it back) and with an LM attached (the fuser re-picks
+        on standardised scores, in which a bonus in log-prob units has no defined place)."""
         if phrases is None or len(phrases) == 0:
             self.engine.set_bias(None)
             return
         if self.engine.beam > 1:
-            raise ValueError("set_hotwords needs greedy decode (beam = 1): a hypothesis slot would have to carry its automaton node "
-                             "through the beam's parent indirection")
+            raise ValueError("set_hotwords needs greedy decode (beam = 1); a beam engine has set_beam_hotwords")
         if self.engine.lm_cfg is not None:
             raise ValueError("set_hotwords refuses an attached LM: the fuser re-picks on standardised scores, in which a bonus in "
                              "log-prob units has no defined place")
@@ -159,6 +165,31 @@ class LibreASR:
         if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
             raise ValueError("set_hotwords: phrases of at least one token, boosts finite and >= 0")
         self.engine.set_bias(self.engine.bias_compile(ids, w))
+
+    def set_beam_hotwords(self, phrases, boost=1.0):
+        """Contextual biasing of beam search (transcribe and stream alike): a hypothesis that matches a listed phrase token by token
+        gains the phrase's boost in its RANKING score, spread over the tokens, and a partial match that fails hands back what it
+        had gained -- so the bonus demotes as well as promotes, which greedy decode (set_hotwords) cannot do.  phrases and boost
+        follow set_hotwords' rules: lists of non-blank token ids or text, one float or one per phrase, finite and >= 0, in
+        log-prob units per matched token.  None or [] clears.  The default 1.0 is a PLACEHOLDER for a knob nobody has tuned on
+        real data: choose a value on held-out audio.  With hotwords set, offline transcribe(nbest=...) results carry "bonus" (the
+        summed gain of the hypothesis); "score" stays the ranking score.  Streams do not report the bonus: a frozen prefix hides
+        where resets fell.  Raises ValueError on a greedy engine (it has set_hotwords) and with an LM attached (the combination
+        is not served)."""
+        if self.engine.beam <= 1:
+            raise ValueError("set_beam_hotwords needs a beam engine (beam > 1); greedy decode has set_hotwords")
+        if phrases is None or len(phrases) == 0:
+            self.engine.set_beam_bias(None)
+            return
+        if self.engine.lm_cfg is not None:
+            raise ValueError("set_beam_hotwords refuses an attached LM: the combination with LM fusion is not served")
+        ids = [self._ids(p) for p in phrases]
+        w = [float(boost)] * len(ids) if np.ndim(boost) == 0 else [float(b) for b in boost]
+        if len(w) != len(ids):
+            raise ValueError("boost: one float, or one per phrase")
+        if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
+            raise ValueError("set_beam_hotwords: phrases of at least one token, boosts finite and >= 0")
+        self.engine.set_beam_bias(self.engine.beam_bias_compile(ids, w))
 
     def _posteriors(self, r):
         """per token of an align_pcm(posteriors=True) or align_band_post_pcm result: the lattice's view of where the token is, over all

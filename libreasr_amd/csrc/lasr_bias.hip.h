@@ -129,4 +129,129 @@ inline const char* validate(int n_nodes, const int32_t* edge_off, const int32_t*
     return nullptr;
 }
 
+// ---------------------------------------------------------------------------- the graph in beam form
+// A beam ranks by score, so the bonus of a partial match is revocable: term(v) = some phrase ends exactly at v; cum(v) = the summed
+// w along path(v); held(v) = the part of it collected since the last completed phrase on the path (0 at a term node).  An edge
+// (v, a, n = delta(v, a)) gains w(n) where n is v's trie child, and cum(n) - held(v) on a failure transition (the held part is handed
+// back, the new match is paid from its start); a non-blank token that is not listed gains back[v] = -held(v) and leads to the root.
+// Sums in double in path order (parent[v] < v), every gain and back rounded once to f32.
+constexpr float BEAM_GAIN_MAX = 1000.0f;      // bound on |gain| and |back| (k_beam_select_rw's pruning argument relies on it)
+
+inline bool gain_ok(float g) { return g >= -BEAM_GAIN_MAX && g <= BEAM_GAIN_MAX; }      // (NaN fails both comparisons)
+
+// the body of lasr_beam_bias_compile (include/lasr.h)
+inline int beam_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
+                        int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_gain, float* node_back,
+                        int32_t* depth, int* n_nodes, int* n_edges) {
+    if (n_nodes) *n_nodes = 0;
+    if (n_edges) *n_edges = 0;
+    if (!tokens || !n_tokens || !weights || !edge_off || !edge_tok || !edge_next || !edge_gain || !node_back || !n_nodes || !n_edges || k < 1)
+        return B_EINVAL;
+    long long total = 0;
+    for (int j = 0; j < k; ++j) {
+        if (n_tokens[j] < 1 || !weight_ok(weights[j])) return B_EINVAL;
+        total += n_tokens[j];
+        if (total >= (1ll << 31) - 1) return B_EINVAL;
+    }
+    for (long long i = 0; i < total; ++i)
+        if (tokens[i] < 0 || tokens[i] >= vocab || tokens[i] == blank) return B_EINVAL;
+    Graph g;
+    if (!build(tokens, n_tokens, weights, k, g)) return B_EINVAL;
+    const int n = (int)g.off.size() - 1, e = (int)g.tok.size();
+    // the same tree once more for parent and term (lasr_prefix_tree's numbering is build's)
+    lasr_pt::Tree t;
+    lasr_pt::build(tokens, n_tokens, k, t);
+    std::vector<char> term(n, 0);
+    for (int j = 0; j < k; ++j) term[t.term[j]] = 1;
+    std::vector<float> w(n, 0.0f);
+    for (int v = 0; v < n; ++v)
+        for (int32_t i = g.off[v]; i < g.off[v + 1]; ++i)
+            if (t.parent[g.next[i]] == v) w[g.next[i]] = g.bonus[i];
+    std::vector<double> cum(n, 0.0), held(n, 0.0);
+    for (int v = 1; v < n; ++v) {
+        cum[v] = cum[t.parent[v]] + (double)w[v];
+        held[v] = term[v] ? 0.0 : held[t.parent[v]] + (double)w[v];
+    }
+    std::vector<float> gain(e), back(n);
+    for (int v = 0; v < n; ++v) {
+        back[v] = (float)(-held[v]);
+        if (!gain_ok(back[v])) return B_EINVAL;
+        for (int32_t i = g.off[v]; i < g.off[v + 1]; ++i) {
+            const int nx = g.next[i];
+            gain[i] = t.parent[nx] == v ? w[nx] : (float)(cum[nx] - held[v]);
+            if (!gain_ok(gain[i])) return B_EINVAL;
+        }
+    }
+    *n_nodes = n; *n_edges = e;
+    if (n > cap_nodes || e > cap_edges) return B_EFULL;
+    for (int v = 0; v <= n; ++v) edge_off[v] = g.off[v];
+    for (int i = 0; i < e; ++i) { edge_tok[i] = g.tok[i]; edge_next[i] = g.next[i]; edge_gain[i] = gain[i]; }
+    for (int v = 0; v < n; ++v) node_back[v] = back[v];
+    if (depth) for (int v = 0; v < n; ++v) depth[v] = g.depth[v];
+    return B_OK;
+}
+
+// lasr_set_beam_bias' checks of a caller's graph (nullptr: fine, else what is wrong): validate's, but a gain may have either sign
+inline const char* validate_beam(int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_gain,
+                                 const float* node_back, int vocab, int blank) {
+    if (n_nodes < 1 || n_nodes > MAX_NODES) return "n_nodes outside [1, 65536]";
+    if (!edge_off) return "null edge_off";
+    if (!node_back) return "null node_back";
+    if (edge_off[0] != 0) return "edge_off[0] != 0";
+    for (int v = 0; v < n_nodes; ++v)
+        if (edge_off[v + 1] < edge_off[v]) return "edge_off decreases";
+    const long long e = edge_off[n_nodes];
+    if (e > MAX_EDGES) return "more than 2^22 edges";
+    if (e > 0 && (!edge_tok || !edge_next || !edge_gain)) return "null edge array";
+    if (node_back[0] != 0.0f) return "node_back[0] != 0";
+    for (int v = 0; v < n_nodes; ++v) {
+        if (!(node_back[v] <= 0.0f) || !gain_ok(node_back[v])) return "node_back positive, not finite or below -1000";
+        for (int32_t i = edge_off[v]; i < edge_off[v + 1]; ++i) {
+            if (edge_tok[i] < 0 || edge_tok[i] >= vocab) return "edge token outside the vocabulary";
+            if (edge_tok[i] == blank) return "blank listed as an edge";
+            if (i > edge_off[v] && edge_tok[i] <= edge_tok[i - 1]) return "edge tokens of a node not ascending";
+            if (edge_next[i] < 1 || edge_next[i] >= n_nodes) return "edge target outside [1, n_nodes)";
+            if (!gain_ok(edge_gain[i])) return "edge gain not finite or beyond 1000";
+        }
+    }
+    return nullptr;
+}
+
+// the edge of node v by token a (its index, -1: not listed): binary search in the node's ascending token list
+inline int find_edge(const int32_t* edge_off, const int32_t* edge_tok, int v, int32_t a) {
+    int lo = edge_off[v], hi = edge_off[v + 1];
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (edge_tok[mid] < a) lo = mid + 1; else hi = mid;
+    }
+    return lo < edge_off[v + 1] && edge_tok[lo] == a ? lo : -1;
+}
+
+// the body of lasr_bias_walk (include/lasr.h): tokens through a beam-form graph from `start`
+inline int walk(int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_gain,
+                const float* node_back, int blank, const int32_t* tokens, int n, int start, int* end_node, double* total, float* gains) {
+    if (n_nodes < 1 || !edge_off || !node_back || n < 0 || (n > 0 && !tokens) || start < 0 || start >= n_nodes) return B_EINVAL;
+    if (edge_off[n_nodes] > 0 && (!edge_tok || !edge_next || !edge_gain)) return B_EINVAL;
+    int v = start;
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        float gn = 0.0f;
+        if (tokens[i] < 0) return B_EINVAL;
+        if (tokens[i] != blank) {
+            const int e = find_edge(edge_off, edge_tok, v, tokens[i]);
+            if (e >= 0) {
+                if (edge_next[e] < 0 || edge_next[e] >= n_nodes) return B_EINVAL;
+                gn = edge_gain[e]; v = edge_next[e];
+            } else {
+                gn = node_back[v]; v = 0;
+            }
+        }
+        sum += (double)gn;
+        if (gains) gains[i] = gn;
+    }
+    if (end_node) *end_node = v;
+    if (total) *total = sum;
+    return B_OK;
+}
+
 }  // namespace lasr_bias

@@ -313,6 +313,14 @@ struct lasr_ctx {
     int* bias_tab = nullptr;
     int* bias_node_dev = nullptr;         // [M]
     int* bias_pick_dev = nullptr;         // [M]
+    // contextual biasing in the beam (lasr_set_beam_bias): the graph in beam form, one device block [off | tok | next |
+    // gain | back] (beam_state() points BeamState's bias_* into it; bbias_nodes != 0 is "on"), every hypothesis slot's node (kept once
+    // allocated) and lasr_beam_bias_round's scratch BeamState (kept once allocated)
+    int bbias_nodes = 0;
+    size_t bbias_edges = 0;
+    int* bbias_tab = nullptr;
+    int* b_bias_node = nullptr;           // [Md]
+    double* bbias_round_dev = nullptr;    // lasr_beam_bias_round: [Md] scores, then the int rows (see there)
 
     // in-job timing of the dominant kernel (lasr_cell_prof): one HIP-event pair around the encoder-cell sequence of
     // every model step, on the stream the cells are launched on; harvested lazily (ring of pairs)

@@ -25,6 +25,7 @@ int apply_reset(lasr_ctx* c, const DecView& v, bool any_pred, int mask = 3, bool
     }
     a.token = c->ds.token; a.emit = c->ds.emit;
     a.bias_node = c->ds.bias_node;           // (null unless a graph is attached: greedy contexts only)
+    if (beam && c->bbias_nodes) a.bias_node = c->b_bias_node;      // (lasr_set_beam_bias: the W slots' nodes restart with the predictor)
     const bool use_bos = c->bos_ready && !beam && !plain_rows && c->W == 1 && (mask & 2);
     if (use_bos) {
         for (int l = 0; l < a.Lp; ++l) { a.bos_h[l] = c->bos_h[l]; a.bos_c[l] = c->d.pred_cell ? c->bos_c[l] : nullptr; }
@@ -227,6 +228,13 @@ BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
     b.t_idx = v.t_idx; b.T_row = v.T_row;
     b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit; b.parent = c->b_parent;
     if (c->beam_merge) { b.seq_hash = c->b_seq_hash; b.seq_len = c->b_seq_len; }
+    if (c->bbias_nodes) {                     // (lasr_set_beam_bias: the BIAS instantiations)
+        const int* tab = c->bbias_tab;
+        const size_t n = (size_t)c->bbias_nodes, E = c->bbias_edges;
+        b.bias_node = c->b_bias_node;
+        b.bias_off = tab; b.bias_tok = tab + n + 1; b.bias_next = tab + n + 1 + E;
+        b.bias_gain = (const float*)(tab + n + 1 + 2 * E); b.bias_back = (const float*)(tab + n + 1 + 3 * E);
+    }
     if (!cont) {
         b.iters = c->ds.iters; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;
         b.dbg = c->dbg ? c->dbg + (size_t)4 * 4096 * 16 : nullptr;      // reuses the "logits" slot of the debug buffer

@@ -2149,8 +2149,8 @@ int lasr_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const floa
 int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_bonus) {
     if (!c) return LASR_EINVAL;
     if (c->W > 1)
-        return fail(c, LASR_EINVAL, "contextual biasing serves greedy decode (beam = 1): a hypothesis slot would have to carry its node through "
-                                    "the parent indirection and merging would have to include it in the identity");
+        return fail(c, LASR_EINVAL, "lasr_set_bias serves greedy decode (beam = 1); beam search has lasr_set_beam_bias, where the bonus is "
+                                    "part of the ranking score");
     if (n_nodes == 0 && !c->ds.bias_node) return LASR_OK;       // (off already: also fine while steps are in flight)
     if (n_nodes != 0) {
         if (c->lm.on)
@@ -2202,6 +2202,134 @@ int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes) {
     std::vector<int> all((size_t)c->M);
     HIPCHK(c, hipMemcpy(all.data(), c->bias_node_dev, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) nodes[i] = all[slots[i]];
+    return LASR_OK;
+}
+
+// ---------------------------------------------------------------------------- contextual biasing in the beam
+int lasr_beam_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
+                           int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_gain, float* node_back,
+                           int32_t* depth, int* n_nodes, int* n_edges) {
+    return lasr_bias::beam_compile(tokens, n_tokens, weights, k, vocab, blank, cap_nodes, cap_edges, edge_off, edge_tok, edge_next, edge_gain,
+                                   node_back, depth, n_nodes, n_edges);
+}
+int lasr_bias_walk(int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_gain,
+                   const float* node_back, int blank, const int32_t* tokens, int n, int start, int* end_node, double* total, float* gains) {
+    return lasr_bias::walk(n_nodes, edge_off, edge_tok, edge_next, edge_gain, node_back, blank, tokens, n, start, end_node, total, gains);
+}
+// Beam search: with a graph attached the selection rounds run k_beam_select_rw<.., BIAS = true>, and every hypothesis slot carries
+// its automaton node through the parent indirection (BeamState::bias_node; null = off, the default).  Like lasr_set_beam_merge this
+// changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  The graph is checked
+// on the host before anything changes.  The scores stay what they are, at switch-on and at switch-off.
+int lasr_set_beam_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next,
+                       const float* edge_gain, const float* node_back) {
+    if (!c) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_set_beam_bias serves beam search (beam > 1); greedy decode has lasr_set_bias");
+    if (n_nodes == 0 && !c->bbias_nodes) return LASR_OK;        // (off already: also fine while steps are in flight)
+    if (n_nodes != 0) {
+        if (c->lm.on) return fail(c, LASR_ESTATE, "lasr_set_beam_bias refuses an attached LM (the combination with LM fusion is not served)");
+        const char* bad = lasr_bias::validate_beam(n_nodes, edge_off, edge_tok, edge_next, edge_gain, node_back, c->d.vocab, c->d.blank);
+        if (bad) return fail(c, LASR_EINVAL, "lasr_set_beam_bias: %s", bad);
+    }
+    RC(toggle_prologue(c, "slot %d holds a result that was not fetched: fetch it before the switch"));
+    int* tab = nullptr;
+    size_t E = 0;
+    if (n_nodes) {
+        E = (size_t)edge_off[n_nodes];
+        std::vector<int> img((size_t)n_nodes + 1 + 3 * E + (size_t)n_nodes);
+        std::copy(edge_off, edge_off + n_nodes + 1, img.begin());
+        if (E) {
+            std::copy(edge_tok, edge_tok + E, img.begin() + n_nodes + 1);
+            std::copy(edge_next, edge_next + E, img.begin() + n_nodes + 1 + E);
+            memcpy(img.data() + n_nodes + 1 + 2 * E, edge_gain, sizeof(float) * E);
+        }
+        memcpy(img.data() + n_nodes + 1 + 3 * E, node_back, sizeof(float) * (size_t)n_nodes);
+        RC(upload(c, &tab, (const int*)img.data(), img.size()));
+        if (!c->b_bias_node) RC(dalloc(c, &c->b_bias_node, (size_t)c->Md));
+        HIPCHK(c, hipMemset(c->b_bias_node, 0, sizeof(int) * (size_t)c->Md));      // every slot starts over at the root
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    dfree(c, c->bbias_tab);
+    c->bbias_tab = tab;
+    c->bbias_nodes = n_nodes;
+    c->bbias_edges = E;
+    return LASR_OK;
+}
+
+int lasr_beam_bias_state(lasr_ctx* c, int slot, int32_t* nodes) {
+    if (!c) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_beam_bias_state serves beam search (beam > 1); greedy decode has lasr_bias_state");
+    if (!c->bbias_nodes) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    RC(open_slot(c, slot));
+    if (!nodes) return fail(c, LASR_EINVAL, "null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    std::vector<int> nd((size_t)c->W), al((size_t)c->W);
+    HIPCHK(c, hipMemcpy(nd.data(), c->b_bias_node + (size_t)slot * c->W, sizeof(int) * nd.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(al.data(), c->b_alive + (size_t)slot * c->W, sizeof(int) * al.size(), hipMemcpyDeviceToHost));
+    for (int j = 0; j < c->W; ++j) nodes[j] = al[j] ? nd[j] : -1;
+    return LASR_OK;
+}
+
+// one biased selection round on the caller's logits and slot state with the attached graph: the decode loop's own
+// k_beam_select_rw<WT, true, false, true> on a scratch BeamState (synchronous form, round slot 0) -- no slot's state is read or written
+int lasr_beam_bias_round(lasr_ctx* c, const float* logits, int n, const double* score, const int32_t* alive, const int32_t* inB,
+                         const int32_t* node, const int32_t* rounds, int max_iters, int32_t* parent, int32_t* token, int32_t* emit,
+                         double* score_out, int32_t* alive_out, int32_t* inB_out, int32_t* node_out, float* term) {
+    if (!c) return LASR_EINVAL;
+    if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_beam_bias_round serves beam search (beam > 1); greedy decode has lasr_bias_pick");
+    if (!logits || !score || !alive || !inB || !node || !rounds || !parent || !token || !emit || !score_out || !alive_out || !inB_out ||
+        !node_out || !term || n < 1 || n > c->d.max_streams || max_iters < 1)
+        return fail(c, LASR_EINVAL, "bad argument");
+    if (!c->bbias_nodes) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
+    const int W = c->W, M = c->M;
+    const size_t Md = (size_t)c->Md, nW = (size_t)n * W;
+    for (size_t r = 0; r < nW; ++r)
+        if (node[r] < 0 || node[r] >= c->bbias_nodes) return fail(c, LASR_EINVAL, "row %zu: node %d outside [0, %d)", r, node[r], c->bbias_nodes);
+    for (int q = 0; q < n; ++q)
+        if (rounds[q] < 0) return fail(c, LASR_EINVAL, "stream %d: %d rounds done", q, rounds[q]);
+    RC(flush_lazy(c));
+    RC(require_idle(c));
+    HIPCHK(c, hipSetDevice(c->device));
+    // scratch: [Md] doubles (score), then int rows: alive, inB, node, token, emit, parent, trellis [Md each], rec [2 Md],
+    // iters, t_idx, T_row [M each], unfinished [1]
+    const size_t n_int = 9 * Md + 3 * (size_t)M + 1;
+    if (!c->bbias_round_dev) RC(dalloc(c, &c->bbias_round_dev, Md + (n_int + 1) / 2));
+    static_assert(sizeof(BeamRec) == 2 * sizeof(int), "BeamRec is two words");
+    double* d_sc = c->bbias_round_dev;
+    int* d_i = (int*)(d_sc + Md);
+    std::vector<double> h_sc(Md, -INFINITY);
+    std::vector<int> h_i(n_int, 0);
+    std::copy(score, score + nW, h_sc.begin());
+    for (size_t r = 0; r < nW; ++r) { h_i[r] = alive[r] ? 1 : 0; h_i[Md + r] = inB[r] ? 1 : 0; h_i[2 * Md + r] = node[r]; }
+    for (int q = 0; q < n; ++q) { h_i[9 * Md + q] = rounds[q]; h_i[9 * Md + 2 * (size_t)M + q] = 1; }      // (t_idx 0, T_row 1: one frame to decode)
+    HIPCHK(c, hipMemcpyAsync(d_sc, h_sc.data(), sizeof(double) * Md, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_i, h_i.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, c->stream));
+    DecView v = sync_view(c, c->la_sync);
+    BeamState b = beam_state(c, v, false, max_iters);
+    b.score = d_sc; b.alive = d_i; b.inB = d_i + Md; b.bias_node = d_i + 2 * Md; b.token = d_i + 3 * Md; b.emit = d_i + 4 * Md;
+    b.parent = d_i + 5 * Md; b.trellis = d_i + 6 * Md; b.rec = (BeamRec*)(d_i + 7 * Md);
+    b.iters = d_i + 9 * Md; b.t_idx = d_i + 9 * Md + M; b.T_row = d_i + 9 * Md + 2 * (size_t)M; b.unfinished = d_i + 9 * Md + 3 * (size_t)M;
+    b.seq_hash = nullptr; b.seq_len = nullptr; b.dbg = nullptr;
+    b.lm_on = 0; b.done2 = nullptr;
+    with_const<2, 4, 8>(W, [&](auto wt) {
+        constexpr int WT = decltype(wt)::value;
+        hipLaunchKernelGGL((k_beam_select_rw<WT, true, false, true>), dim3(n), dim3(64 * WT), 0, c->stream, logits, b, 0);      // (n workgroups: the caller's logits end there)
+    });
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_sc.data(), d_sc, sizeof(double) * Md, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_i.data(), d_i, sizeof(int) * n_int, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t r = 0; r < nW; ++r) {
+        score_out[r] = h_sc[r]; alive_out[r] = h_i[r]; inB_out[r] = h_i[Md + r]; node_out[r] = h_i[2 * Md + r];
+        emit[r] = h_i[4 * Md + r]; parent[r] = h_i[5 * Md + r];
+        token[r] = emit[r] ? h_i[3 * Md + r] : -1;
+        float tm = 0.f;
+        if (emit[r]) memcpy(&tm, &h_i[7 * Md + 2 * r + 1], sizeof(float));
+        term[r] = tm;
+    }
     return LASR_OK;
 }
 
@@ -2615,6 +2743,8 @@ static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weig
     if (c->ds.bias_node)
         return fail(c, LASR_ESTATE, "a bias graph is set (the fuser re-picks on standardised scores, in which a bonus in log-prob units has "
                                     "no defined place): lasr_set_bias(c, 0, ...) first");
+    if (c->bbias_nodes)
+        return fail(c, LASR_ESTATE, "a beam bias graph is set (the combination with LM fusion is not served): lasr_set_beam_bias(c, 0, ...) first");
     if (c->beam_merge == 1) return fail(c, LASR_ESTATE, "beam merging is on in the mode that refuses an LM (lasr_set_beam_merge(c, 0) or (c, LASR_BEAM_MERGE_LM) first)");
     if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)

@@ -216,6 +216,7 @@ inline __global__ void k_reset_rows(const ResetArgs a) {
                 if (b) a.emit[rp + b] = 0;
                 if (wh & 2) { a.score[rp + b] = b ? -INFINITY : 0.0; a.alive[rp + b] = b ? 0 : 1; a.inB[rp + b] = 0; }
                 if ((wh & 2) && a.seq_hash) { a.seq_hash[rp + b] = BM_SEED; a.seq_len[rp + b] = 0; }
+                if ((wh & 2) && a.bias_node && b) a.bias_node[rp + b] = 0;      // (beam biasing: every slot's node; slot 0's above)
             }
     }
     const size_t ho = act_off(a.bf, r, u, a.MT);
@@ -1011,6 +1012,16 @@ struct BeamState : ContRound {
     // false> never looks).
     unsigned long long* seq_hash;   // [Md]
     int* seq_len;                   // [Md]
+    // contextual biasing in the beam (lasr_set_beam_bias): every slot's node in the phrase automaton and the graph in
+    // beam form -- CSR edge lists (tokens ascending per node) with a signed gain per edge, and per node the gain of every non-blank
+    // token that is not listed.  bias_node == nullptr: off (k_beam_select_rw<WT, REC, MERGE, false> never looks).  (At the end of
+    // the struct: the kernel-argument offsets of everything above are what they were.)
+    int* bias_node;            // [Md]
+    const int* bias_off;       // [n_nodes + 1]
+    const int* bias_tok;       // [n_edges]
+    const int* bias_next;      // [n_edges] in [1, n_nodes)
+    const float* bias_gain;    // [n_edges] |gain| <= 1000
+    const float* bias_back;    // [n_nodes] in [-1000, 0]
 };
 
 // k_beam_select with ONE WAVE PER HYPOTHESIS ROW (V <= 2048, the 512-thread form's arithmetic): wave b keeps row b's logits in
@@ -1025,7 +1036,15 @@ struct BeamState : ContRound {
 // 0 extends store (t, term) into s.rec.  REC = false is the kernel as it was.
 // MERGE (lasr_set_beam_merge): between the selection of the W survivors and their stores, wave 0 merges the survivors that hold the
 // same tokens (beam_merge_round); a merged-away slot takes the dead-slot path of the stores.  MERGE = false is the kernel as it was.
-template <int WT, bool REC, bool MERGE>
+// BIAS (lasr_set_beam_bias): a row in A adds its node's gains to its log-probs before the ordered top-W passes -- a wave-private
+// LDS row [2048] is filled with back[node] (blank: 0), the wave's lanes scatter the node's edge gains over it, and every lane reads
+// its 32 tokens' values back into the registers it keeps them in (static indices: no scratch).  The wave orders its own LDS
+// writes and reads with a wavefront-scope fence + wave barrier: the code runs only in waves whose row is in A, so no block barrier
+// may stand there.  A pass's winner gets its candidate score as (score + lp) + gain in doubles, lp recomputed from the logit (the
+// same bits as the register held before the gain went in) and the gain re-read from the LDS row; REC's term is that lp.  Wave 0
+// then moves the survivors' nodes: parent's node by v_readlane, delta by a binary search in the node's token list, one plain store
+// per slot in front of publish().  BIAS = false is the kernel as it was.
+template <int WT, bool REC, bool MERGE, bool BIAS>
 __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restrict__ logits, BeamState s, int iter_slot) {
     constexpr int VW = 8, KEEP = 4, NTV = 512;      // virtual waves / slots per virtual thread / virtual threads (the old layout)
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1063,6 +1082,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     __shared__ double cand_sc[WT][WT];
     __shared__ int cand_ord[WT][WT];
     __shared__ float cand_lp[REC ? WT : 1][REC ? WT : 1];      // (read only where cand_sc holds a candidate of the same round)
+    __shared__ float gain_row[BIAS ? WT : 1][BIAS ? VW * KEEP * 64 : 1];      // (BIAS) per wave: the gain of every token at the row's node
     // (the table starts empty: a wave that looks at it while others are still writing -- the pruning below -- sees "no candidate")
     if (tid < WT * WT) { cand_sc[tid / WT][tid % WT] = -INFINITY; cand_ord[tid / WT][tid % WT] = 0x7fffffff; }
     __syncthreads();
@@ -1071,6 +1091,9 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     const double scb = in ? s.score[r0 + b] : -INFINITY;
     const int alb = in ? s.alive[r0 + b] : 0, ibb = in ? s.inB[r0 + b] : 0;
     const bool inA = alb && !ibb;                    // wave-uniform
+    // (BIAS) the row's node, read in front of the barrier behind which wave 0 stores the new ones
+    int node_b = 0;
+    if constexpr (BIAS) { if (in) node_b = s.bias_node[r0 + b]; }
     if (dbg) s.dbg[1] = wall_clock64();
     if (!inA) {
 #pragma unroll
@@ -1126,6 +1149,25 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
                     if (v != s.blank && v != nb_arg) zl[vw][k] = -INFINITY;
                 }
             }
+        if constexpr (BIAS) {
+            float* gr = gain_row[b];
+            const float bk = s.bias_back[node_b];
+#pragma unroll
+            for (int vw = 0; vw < VW; ++vw)
+#pragma unroll
+                for (int k = 0; k < KEEP; ++k) {
+                    const int v = lane + 64 * vw + NTV * k;
+                    gr[v] = v == s.blank ? 0.f : bk;
+                }
+            // the wave's own LDS traffic is issued in order; the fence + wave barrier keep the compiler from moving it
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int e = s.bias_off[node_b] + lane, ee = s.bias_off[node_b + 1]; e < ee; e += 64) gr[s.bias_tok[e]] = s.bias_gain[e];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int vw = 0; vw < VW; ++vw)
+#pragma unroll
+                for (int k = 0; k < KEEP; ++k) zl[vw][k] = __fadd_rn(zl[vw][k], gr[lane + 64 * vw + NTV * k]);      // s(j); padding stays -inf
+        }
         // Two levels per lane: the best of each group k (its 8 tokens lane + 64 vw + 512 k, ascending v) is kept beside the values,
         // so a pass compares 4 group heads instead of 32 values, and only the winner's group (wave-uniform index) is rescanned.
         // Ascending v inside a group and ascending k across groups: among equal log p the lower token comes first, as before.
@@ -1148,9 +1190,16 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
                 if (gm[k] > best) { best = gm[k]; arg = ga[k]; }
             wave_argmax_f32(best, arg);
             if (!(best > -INFINITY)) break;           // the row's candidates are exhausted (wave-uniform)
-            const double myv = scb + (double)best;
+            double myv = scb + (double)best;
+            float term = best;
+            if constexpr (BIAS) {
+                // the winner's unbiased log p: its logit once more (L2-hot) through the line that made the register -- the same
+                // bits; best - gain in f32 would not be.  The candidate: (score + lp) + gain, in that order.
+                term = (logits[(size_t)(r0 + b) * V + arg] - m) - lg;
+                myv = (scb + (double)term) + (double)gain_row[b][arg];
+            }
             if (lane == 0) {
-                if constexpr (REC) cand_lp[b][j] = best;        // (before the score: a reader that sees the candidate finds its term; wave 0 reads behind the barrier anyway)
+                if constexpr (REC) cand_lp[b][j] = term;        // (before the score: a reader that sees the candidate finds its term; wave 0 reads behind the barrier anyway)
                 cand_sc[b][j] = myv; cand_ord[b][j] = b * (V + 1) + 1 + arg;
             }
             {
@@ -1161,7 +1210,17 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
                 // (the margin makes the count immune to a torn 64-bit read, should the hardware ever split one: a half-written entry
                 //  is a NaN or the new value with its low word zero, 2^-20 relative off)
                 const double other = lane < WT * WT ? ((const volatile double*)&cand_sc[0][0])[lane] : -INFINITY;
-                if (__popcll(__ballot(other - myv > 1e-3 + 2e-6 * fabs(myv))) >= W) break;
+                // (BIAS) The row offers in descending f32 s = fl(lp + g) while the table holds the doubles d = lp + g (exact in
+                // double for |g| <= 1000 and any lp that matters).  Rounding is monotone: a later offer with s' < s has d' <= d;
+                // one with s' == s lies in the same rounding interval, so d' <= d + ulp(s) <= d + 2^-23 |s|.  The bound below
+                // grows by that much, so "W others beat this one by more than the bound" still says that they beat every later
+                // offer of the row strictly.  (For |s| < 8e3 the fixed 1e-3 alone would cover it; a row with a log p of -1e4 and
+                // an equal-s neighbour is the case the term is there for.)
+                if constexpr (BIAS) {
+                    if (__popcll(__ballot(other - myv > (1e-3 + 2e-6 * fabs(myv)) + (double)(1.1920929e-7f * fabsf(best)))) >= W) break;
+                } else {
+                    if (__popcll(__ballot(other - myv > 1e-3 + 2e-6 * fabs(myv))) >= W) break;
+                }
             }
             const int kk = arg / NTV, vv = (arg - kk * NTV) >> 6;       // wave-uniform (the winner is)
             const bool mine = (arg & 63) == lane;                       // the winner's lane takes it out of its group
@@ -1186,6 +1245,9 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     unsigned long long id_hash = BM_SEED;
     int id_len = 0;
     if constexpr (MERGE) { if (lane < W) { id_hash = s.seq_hash[r0 + lane]; id_len = s.seq_len[r0 + lane]; } }
+    // (BIAS) likewise this lane's own slot's node (wave 0's row is slot 0: lane j reads slot j's)
+    int my_node = 0;
+    if constexpr (BIAS) { if (lane < W) my_node = s.bias_node[r0 + lane]; }
     // ---- the ordered top-W of the WT x WT candidate table, by wave 0 (round 6; one thread before: W passes over W list heads + W
     // slots of bookkeeping = 3.1 us of 7.6 at W = 4, 7.6 of 13.3 at W = 8).  Lane l holds candidate (row l / WT, position l % WT); its
     // rank = the number of candidates that come before it in the total order (score descending, ordinal ascending: ordinals are
@@ -1224,6 +1286,22 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     bool live = slot && sel > -INFINITY;
     if constexpr (MERGE) beam_merge_round<WT>(lane, W, V, s.blank, round >= s.max_iters, id_hash, id_len, sord, live, sel, s.seq_hash + r0, s.seq_len + r0);
     int inb = 1;
+    if constexpr (BIAS) {
+        // the survivor's node: its parent's (v_readlane over the WT slots, every lane of the wave takes part), moved along
+        // delta(parent's node, token) where the slot was extended by a non-blank token; a dead slot's is 0
+        const int pb = live ? sord / (V + 1) : 0, k = live ? sord - pb * (V + 1) : 0;
+        int pn = 0;
+#pragma unroll
+        for (int j = 0; j < WT; ++j) { const int nj = __builtin_amdgcn_readlane(my_node, j); if (pb == j) pn = nj; }
+        int nn = live ? pn : 0;
+        if (live && k > 0 && k - 1 != s.blank) {
+            int lo = s.bias_off[pn], hi = s.bias_off[pn + 1];
+            const int end = hi;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (s.bias_tok[mid] < k - 1) lo = mid + 1; else hi = mid; }
+            nn = lo < end && s.bias_tok[lo] == k - 1 ? s.bias_next[lo] : 0;
+        }
+        if (slot) s.bias_node[r0 + lane] = nn;      // (a plain store: the round's release orders it like seq_hash)
+    }
     if (slot) {
         const int r = r0 + lane;
         if (!live) {

@@ -65,6 +65,61 @@ def bias_compile(lib, phrases, weights, vocab, blank):
     return BiasGraph(off, etok[:ne.value], enxt[:ne.value], ebon[:ne.value], dep)
 
 
+class BeamBiasGraph:
+    """The phrase automaton in beam form, lasr_set_beam_bias' layout: BiasGraph's CSR lists with a signed gain per edge and, per
+    node, the gain of every non-blank token that is not listed (node_back <= 0)."""
+
+    def __init__(self, edge_off, edge_tok, edge_next, edge_gain, node_back, depth=None):
+        self.edge_off = np.ascontiguousarray(edge_off, dtype=np.int32)
+        self.edge_tok = np.ascontiguousarray(edge_tok, dtype=np.int32)
+        self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32)
+        self.edge_gain = np.ascontiguousarray(edge_gain, dtype=np.float32)
+        self.node_back = np.ascontiguousarray(node_back, dtype=np.float32)
+        self.depth = None if depth is None else np.ascontiguousarray(depth, dtype=np.int32)
+        self.n_nodes = int(self.edge_off.size) - 1
+        self.n_edges = int(self.edge_tok.size)
+
+
+def beam_bias_compile(lib, phrases, weights, vocab, blank):
+    """lasr_beam_bias_compile (no context, no GPU): sized by a first call with no room, filled by the second"""
+    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+    k = len(toks)
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if k < 1 or w.size != k:
+        raise ValueError("beam_bias_compile: at least one phrase and one weight per phrase")
+    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
+    nn, ne = C.c_int(0), C.c_int(0)
+    one = [np.zeros(1, np.int32) for _ in range(3)] + [np.zeros(1, np.float32), np.zeros(1, np.float32)]
+    rc = lib.lasr_beam_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), 0, 0, _ptr(one[0]), _ptr(one[1]),
+                                    _ptr(one[2]), _ptr(one[3]), _ptr(one[4]), None, C.byref(nn), C.byref(ne))
+    if rc != N.LASR_EFULL:
+        raise N.LasrError(rc, "lasr_beam_bias_compile: phrases of >= 1 ids in [0, vocab) other than blank, weights finite and >= 0, "
+                              "no gain beyond 1000")
+    e = max(ne.value, 1)
+    off, dep, back = np.zeros(nn.value + 1, np.int32), np.zeros(nn.value, np.int32), np.zeros(nn.value, np.float32)
+    etok, enxt, egain = np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.float32)
+    rc = lib.lasr_beam_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), nn.value, ne.value, _ptr(off), _ptr(etok),
+                                    _ptr(enxt), _ptr(egain), _ptr(back), _ptr(dep), C.byref(nn), C.byref(ne))
+    if rc != 0:
+        raise N.LasrError(rc, "lasr_beam_bias_compile")
+    return BeamBiasGraph(off, etok[:ne.value], enxt[:ne.value], egain[:ne.value], back, dep)
+
+
+def bias_walk(lib, graph, tokens, blank, start=0):
+    """lasr_bias_walk (no context, no GPU): tokens through a BeamBiasGraph from node `start` -> (end node, the double sum of the
+    f32 gains in order, the gains float32 [n])"""
+    tok = np.ascontiguousarray(np.asarray(tokens, dtype=np.int32).reshape(-1))
+    gains = np.zeros(max(tok.size, 1), np.float32)
+    end, total = C.c_int(0), C.c_double(0.0)
+    rc = lib.lasr_bias_walk(int(graph.n_nodes), _ptr(graph.edge_off), _ptr(graph.edge_tok), _ptr(graph.edge_next), _ptr(graph.edge_gain),
+                            _ptr(graph.node_back), int(blank), _ptr(tok), int(tok.size), int(start), C.byref(end), C.byref(total),
+                            _ptr(gains))
+    if rc != 0:
+        raise N.LasrError(rc, "lasr_bias_walk: start in [0, n_nodes), tokens >= 0")
+    return end.value, total.value, gains[:tok.size]
+
+
 class Engine:
     def __init__(self, state_dict, cfg=None, max_streams=64, device=0, max_iters_offline=3,
                  max_iters_stream=10, blank=0, bos=2, dtype="f32", beam=1, **frontend):
@@ -88,6 +143,7 @@ class Engine:
         self.dtype = dtype
         d.beam = int(beam)                         # 1 = greedy; 2..8 = beam search (both protocols)
         self.beam = int(beam)
+        self.beam_bias = None                      # the BeamBiasGraph attached by set_beam_bias
         for k, v in fe.items():
             setattr(d, k, int(v))
         d.max_streams = int(max_streams)
@@ -779,6 +835,58 @@ class Engine:
         tok, nxt, lp = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.float32)
         self._chk(self.lib.lasr_bias_pick(self.ctx, _ptr(logits), _ptr(nd), B, _ptr(tok), _ptr(nxt), _ptr(lp)))
         return tok, nxt, lp
+
+    # ------------------------------------------------------------------ contextual biasing in the beam
+    def beam_bias_compile(self, phrases, weights):
+        """Phrases (token-id lists) and one weight each (log-prob units, finite, >= 0) -> BeamBiasGraph, the phrase automaton in
+        beam form (lasr_beam_bias_compile, host only; include/lasr.h has the definition)."""
+        return beam_bias_compile(self.lib, phrases, weights, self.desc.vocab, self.desc.blank)
+
+    def set_beam_bias(self, graph):
+        """Attach a BeamBiasGraph to a beam context (every hypothesis slot is biased and restarts at the root; the scores stay);
+        None turns biasing off.  Needs an idle context and no LM (lasr_set_beam_bias).  The attached graph is kept as
+        self.beam_bias for bias_walk."""
+        if graph is None:
+            self._chk(self.lib.lasr_set_beam_bias(self.ctx, 0, None, None, None, None, None))
+            self.beam_bias = None
+            return
+        self._chk(self.lib.lasr_set_beam_bias(self.ctx, int(graph.n_nodes), _ptr(graph.edge_off), _ptr(graph.edge_tok),
+                                              _ptr(graph.edge_next), _ptr(graph.edge_gain), _ptr(graph.node_back)))
+        self.beam_bias = graph
+
+    def beam_bias_state(self, slot):
+        """-> int32 [beam]: the automaton nodes of the stream's hypothesis slots in slot order, -1 for a dead slot (synchronises)"""
+        out = np.zeros(self.beam, dtype=np.int32)
+        self._chk(self.lib.lasr_beam_bias_state(self.ctx, int(slot), _ptr(out)))
+        return out
+
+    def bias_walk(self, tokens, start=0, graph=None):
+        """Tokens through `graph` (default: the attached one) from node `start` -> (end node, summed gain, gains float32 [n]);
+        host only (lasr_bias_walk).  score - summed gain is a hypothesis' acoustic score."""
+        graph = self.beam_bias if graph is None else graph
+        if graph is None:
+            raise ValueError("bias_walk: no graph attached and none given")
+        return bias_walk(self.lib, graph, tokens, self.desc.blank, start)
+
+    def beam_bias_round(self, logits, score, alive, inB, node, rounds, max_iters):
+        """One biased selection round of n streams: logits [n * beam, vocab] (device f32), per-row score / alive / inB / node and
+        per-stream rounds done -> dict of host arrays parent, token, emit, score, alive, inB, node, term (lasr_beam_bias_round;
+        no slot's state is touched)."""
+        logits = logits.contiguous()
+        R = int(logits.shape[0])
+        sc = np.ascontiguousarray(np.asarray(score, dtype=np.float64).reshape(-1))
+        al, ib, nd = (np.ascontiguousarray(np.asarray(x, dtype=np.int32).reshape(-1)) for x in (alive, inB, node))
+        rd = np.ascontiguousarray(np.asarray(rounds, dtype=np.int32).reshape(-1))
+        n = rd.size
+        if R != n * self.beam or any(x.size != R for x in (sc, al, ib, nd)) or logits.shape[1] != self.desc.vocab or logits.dtype != torch.float32:
+            raise ValueError("beam_bias_round: logits [n * beam, vocab] float32, one score / alive / inB / node per row, rounds [n]")
+        torch.cuda.synchronize(self.device)
+        o = {k: np.zeros(R, np.int32) for k in ("parent", "token", "emit", "alive", "inB", "node")}
+        o["score"], o["term"] = np.zeros(R, np.float64), np.zeros(R, np.float32)
+        self._chk(self.lib.lasr_beam_bias_round(self.ctx, _ptr(logits), n, _ptr(sc), _ptr(al), _ptr(ib), _ptr(nd), _ptr(rd), int(max_iters),
+                                                _ptr(o["parent"]), _ptr(o["token"]), _ptr(o["emit"]), _ptr(o["score"]), _ptr(o["alive"]),
+                                                _ptr(o["inB"]), _ptr(o["node"]), _ptr(o["term"])))
+        return o
 
     def _cat_pcm(self, pcm_list):
         """-> (all utterances concatenated: one device tensor if every one is, else one host array; int64 sample counts)"""
