@@ -141,6 +141,16 @@ class LibreASR:
             transcript = self.lang.numericalize(transcript)
         return [int(t) for t in transcript]
 
+    def _hotwords(self, who, phrases, boost):
+        """the phrases as token-id lists and one boost each, for set_hotwords / set_beam_hotwords (`who`: the name in the text)"""
+        ids = [self._ids(p) for p in phrases]
+        w = [float(boost)] * len(ids) if np.ndim(boost) == 0 else [float(b) for b in boost]
+        if len(w) != len(ids):
+            raise ValueError("boost: one float, or one per phrase")
+        if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
+            raise ValueError(who + ": phrases of at least one token, boosts finite and >= 0")
+        return ids, w
+
     def set_hotwords(self, phrases, boost=2.0):
         """Contextual biasing: greedy decode (transcribe and stream alike) prefers the listed phrases from now on.  phrases: lists
         of non-blank token ids, or text when the language object can numericalize (the rule `align` uses); boost: one float, or
@@ -158,13 +168,7 @@ class LibreASR:
         if self.engine.lm_cfg is not None:
             raise ValueError("set_hotwords refuses an attached LM: the fuser re-picks on standardised scores, in which a bonus in "
                              "log-prob units has no defined place")
-        ids = [self._ids(p) for p in phrases]
-        w = [float(boost)] * len(ids) if np.ndim(boost) == 0 else [float(b) for b in boost]
-        if len(w) != len(ids):
-            raise ValueError("boost: one float, or one per phrase")
-        if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
-            raise ValueError("set_hotwords: phrases of at least one token, boosts finite and >= 0")
-        self.engine.set_bias(self.engine.bias_compile(ids, w))
+        self.engine.set_bias(self.engine.bias_compile(*self._hotwords("set_hotwords", phrases, boost)))
 
     def set_beam_hotwords(self, phrases, boost=1.0):
         """Contextual biasing of beam search (transcribe and stream alike): a hypothesis that matches a listed phrase token by token
@@ -183,13 +187,7 @@ class LibreASR:
             return
         if self.engine.lm_cfg is not None:
             raise ValueError("set_beam_hotwords refuses an attached LM: the combination with LM fusion is not served")
-        ids = [self._ids(p) for p in phrases]
-        w = [float(boost)] * len(ids) if np.ndim(boost) == 0 else [float(b) for b in boost]
-        if len(w) != len(ids):
-            raise ValueError("boost: one float, or one per phrase")
-        if any(len(p) == 0 for p in ids) or not all(np.isfinite(b) and b >= 0 for b in w):
-            raise ValueError("set_beam_hotwords: phrases of at least one token, boosts finite and >= 0")
-        self.engine.set_beam_bias(self.engine.beam_bias_compile(ids, w))
+        self.engine.set_beam_bias(self.engine.beam_bias_compile(*self._hotwords("set_beam_hotwords", phrases, boost)))
 
     def _posteriors(self, r):
         """per token of an align_pcm(posteriors=True) or align_band_post_pcm result: the lattice's view of where the token is, over all

@@ -14,8 +14,8 @@ void launch_beam_select(lasr_ctx* c, const DecView& v, BeamState& b, int iter_sl
     // (b.seq_hash: merging of equal hypotheses, lasr_set_beam_merge -- likewise.  With an LM attached the identities are of the
     //  re-picked tokens: the selection kernel runs its MERGE = false body and k_beam_fuse_merge re-picks, merges and patches)
     const bool fuse_merge = c->lm.on && b.seq_hash;
-    // (b.bias_node: contextual biasing, lasr_set_beam_bias -- likewise; never together with an LM)
-    with_const<0, 1>(b.bias_node ? 1 : 0, [&](auto bia) {
+    // (bias_on: contextual biasing, lasr_set_beam_bias -- likewise; never together with an LM)
+    with_const<0, 1>(bias_on(c) ? 1 : 0, [&](auto bia) {
         with_const<0, 1>(b.seq_hash && !fuse_merge ? 1 : 0, [&](auto mrg) {
             with_const<0, 1>(b.rec ? 1 : 0, [&](auto rec) {
                 with_const<2, 4, 8>(c->W, [&](auto wt) {

@@ -307,20 +307,14 @@ struct lasr_ctx {
     std::vector<long long> slot_frames;   // encoder frames the slot has consumed since lasr_stream_open (either protocol)
     int* align_host = nullptr;            // pinned [frames M x TOKRING][log p M x TOKRING]: k_select's record rings (allocated on first use)
     int* c_frame_ring = nullptr; float* c_logp_ring = nullptr;      // device views of the two halves
-    // contextual biasing (lasr_set_bias): the attached graph, one device block [off | tok | next | bonus] (DecState's
-    // bias_* point into it; ds.bias_node != nullptr is "on"), the per-row nodes, and lasr_bias_pick's node row (both kept once allocated)
-    int bias_nodes = 0;
-    int* bias_tab = nullptr;
-    int* bias_node_dev = nullptr;         // [M]
-    int* bias_pick_dev = nullptr;         // [M]
-    // contextual biasing in the beam (lasr_set_beam_bias): the graph in beam form, one device block [off | tok | next |
-    // gain | back] (beam_state() points BeamState's bias_* into it; bbias_nodes != 0 is "on"), every hypothesis slot's node (kept once
-    // allocated) and lasr_beam_bias_round's scratch BeamState (kept once allocated)
-    int bbias_nodes = 0;
-    size_t bbias_edges = 0;
-    int* bbias_tab = nullptr;
-    int* b_bias_node = nullptr;           // [Md]
-    double* bbias_round_dev = nullptr;    // lasr_beam_bias_round: [Md] scores, then the int rows (see there)
+    // contextual biasing (greedy contexts: lasr_set_bias; beam contexts: lasr_set_beam_bias, DESIGN 5.12 -- the width is
+    // fixed at lasr_create, so one group serves both): the attached graph as one device block (lasr_bias::block_layout; the beam
+    // form has the back column), n_nodes != 0 is "on" (bias_on), and every row's node (greedy [M], beam [Md]; kept once allocated).
+    // c->ds.bias points into the block while a greedy graph is attached; beam_state() points BeamState's view into it
+    struct Bias { int* block = nullptr; int n_nodes = 0; size_t n_edges = 0; bool has_back = false; int* node = nullptr; } bias;
+    // the scratch of the two op-level calls (kept once allocated; a context has one of them)
+    int* bias_pick_dev = nullptr;         // lasr_bias_pick: [node -> next | tok | log p], [M] each
+    double* bias_round_dev = nullptr;     // lasr_beam_bias_round: [Md] scores, then the int rows (see there)
 
     // in-job timing of the dominant kernel (lasr_cell_prof): one HIP-event pair around the encoder-cell sequence of
     // every model step, on the stream the cells are launched on; harvested lazily (ring of pairs)
@@ -400,6 +394,8 @@ struct lasr_ctx {
 // either way: read [p], write [p ^ 1]).
 inline int par_rd(bool beam, int p) { return beam ? p : 0; }
 inline int par_wr(bool beam, int p) { return beam ? p ^ 1 : 0; }
+// a bias graph is attached (lasr_set_bias / lasr_set_beam_bias): the decode launches run the BIAS kernels
+inline bool bias_on(const lasr_ctx* c) { return c->bias.n_nodes != 0; }
 
 namespace {
 

@@ -24,8 +24,7 @@ int apply_reset(lasr_ctx* c, const DecView& v, bool any_pred, int mask = 3, bool
         a.pred_h0[l] = c->pred[l].h0; a.pred_c0[l] = c->pred[l].c0;
     }
     a.token = c->ds.token; a.emit = c->ds.emit;
-    a.bias_node = c->ds.bias_node;           // (null unless a graph is attached: greedy contexts only)
-    if (beam && c->bbias_nodes) a.bias_node = c->b_bias_node;      // (lasr_set_beam_bias: the W slots' nodes restart with the predictor)
+    a.bias_node = bias_on(c) && beam == (c->W > 1) ? c->bias.node : nullptr;      // (the nodes restart with the predictor; a beam's plain rows have none)
     const bool use_bos = c->bos_ready && !beam && !plain_rows && c->W == 1 && (mask & 2);
     if (use_bos) {
         for (int l = 0; l < a.Lp; ++l) { a.bos_h[l] = c->bos_h[l]; a.bos_c[l] = c->d.pred_cell ? c->bos_c[l] : nullptr; }
@@ -213,7 +212,7 @@ void decode_iteration(lasr_ctx* c, DecView& v, const DecState& s, BeamState* b, 
     launch_logits(c, v, c->logits, beam ? c->Md : v.la * c->M, true);
     if (side) side->join(c, v);
     if (beam) launch_beam_select(c, v, *b, it);
-    else launch_select<false>(v.stream, c->M, c->logits, c->d.vocab, c->d.blank, max_iters, v.T_row, s, it, nullptr, nullptr, v.la, c->M);
+    else launch_select<false>(v.stream, c->M, c->logits, c->d.vocab, c->d.blank, max_iters, v.T_row, s, it, nullptr, nullptr, v.la, c->M, bias_on(c));
     if (side) side->fork(c, v, beam);
     launch_predictor(c, v, beam);
     launch_ppj(c, v, beam);
@@ -228,12 +227,9 @@ BeamState beam_state(lasr_ctx* c, const DecView& v, bool cont, int max_iters) {
     b.t_idx = v.t_idx; b.T_row = v.T_row;
     b.score = c->b_score; b.alive = c->b_alive; b.inB = c->b_inB; b.token = c->ds.token; b.emit = c->ds.emit; b.parent = c->b_parent;
     if (c->beam_merge) { b.seq_hash = c->b_seq_hash; b.seq_len = c->b_seq_len; }
-    if (c->bbias_nodes) {                     // (lasr_set_beam_bias: the BIAS instantiations)
-        const int* tab = c->bbias_tab;
-        const size_t n = (size_t)c->bbias_nodes, E = c->bbias_edges;
-        b.bias_node = c->b_bias_node;
-        b.bias_off = tab; b.bias_tok = tab + n + 1; b.bias_next = tab + n + 1 + E;
-        b.bias_gain = (const float*)(tab + n + 1 + 2 * E); b.bias_back = (const float*)(tab + n + 1 + 3 * E);
+    if (bias_on(c)) {                         // (lasr_set_beam_bias: the BIAS instantiations)
+        b.bias.node = c->bias.node;
+        b.bias_back = lasr_bias::view_block(c->bias.block, c->bias.n_nodes, c->bias.n_edges, c->bias.has_back, b.bias);
     }
     if (!cont) {
         b.iters = c->ds.iters; b.trellis = c->b_trellis; b.unfinished = c->ds.unfinished;

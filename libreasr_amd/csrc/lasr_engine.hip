@@ -15,14 +15,14 @@ struct PushSrc;
 static int submit_impl(lasr_ctx* c, const int* slots, int n, const PushSrc* fused, bool* fused_done);
 static int push_submit_impl(lasr_ctx* c, const int* slots, int n, const float* pcm, int flags, long long* ticket, const float* const* rows);
 static int overlap_probe_impl(lasr_ctx* c, int delay_us, double* ratio, hipStream_t sa = nullptr, hipStream_t sb = nullptr);
+#include "lasr_prefix_tree.hip.h"
+#include "lasr_bias.hip.h"            // (ahead of lasr_decode.hip.h: beam_state() views the attached block)
 #include "lasr_cmd.hip.h"
 #include "lasr_fe.hip.h"
 #include "lasr_decode.hip.h"
 #include "lasr_lattice_tables.hip.h"
 #include "lasr_lattice.hip.h"
 #include "lasr_lattice_post.hip.h"
-#include "lasr_prefix_tree.hip.h"
-#include "lasr_bias.hip.h"
 #include "lasr_lattice_tree.hip.h"
 #include "lasr_lm_score.hip.h"
 #include "lasr_weights.hip.h"
@@ -1300,7 +1300,7 @@ static int cont_enqueue(lasr_ctx* c, DecView& v, int G) {
         } else {
             launch_logits(c, v, c->logits, v.la * M, true);
         }
-        launch_select<false>(v.stream, M, c->logits, V, c->d.blank, c->d.max_iters_stream, v.T_row, s, 0, nullptr, nullptr, v.la, M);
+        launch_select<false>(v.stream, M, c->logits, V, c->d.blank, c->d.max_iters_stream, v.T_row, s, 0, nullptr, nullptr, v.la, M, bias_on(c));
         rec(A, [&] { launch_predictor(c, v, false, 0, 1); });
         rec(B, [&] { launch_lm(c, v, false, 0, 1, false); });
         launch_pair(c, v.stream, 0, true, A, B);
@@ -2080,17 +2080,24 @@ int lasr_fetch_many(lasr_ctx* c, const int* slots, int n, int32_t* tokens, int c
     return fetch_many(c, slots, n, tokens, nullptr, nullptr, cap, n_new);
 }
 
-// What both record switches (lasr_set_alignments, lasr_set_beam_records) do first: the engine idle, no slot with an unfetched result
-// (`unfetched`: the refusal's text, with the slot and its token count as arguments), both streams drained, the cached decode groups
-// dropped
-static int toggle_prologue(lasr_ctx* c, const char* unfetched) {
+// What a host read of the resident state and every switch of the decode kernels start from: the deferred append flushed, no step in
+// flight (idle = false: lasr_debug_read looks whatever is in flight), the main and the decode stream drained
+static int drain(lasr_ctx* c, bool idle = true) {
     RC(flush_lazy(c));
-    RC(require_idle(c));
-    for (int s = 0; s < c->M; ++s)
-        if (c->results[s].unfetched()) return fail(c, LASR_ESTATE, unfetched, s, c->results[s].need());
+    if (idle) RC(require_idle(c));
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    return LASR_OK;
+}
+
+// What the record switches (lasr_set_alignments, lasr_set_beam_records) and bias_attach do first: the engine idle and drained, no
+// slot with an unfetched result (`unfetched`: the refusal's text, with the slot and its token count as arguments), the cached decode
+// groups dropped
+static int toggle_prologue(lasr_ctx* c, const char* unfetched) {
+    RC(drain(c));
+    for (int s = 0; s < c->M; ++s)
+        if (c->results[s].unfetched()) return fail(c, LASR_ESTATE, unfetched, s, c->results[s].need());
     std::lock_guard<std::mutex> lk(c->mu);        // (the pump thread looks graphs up under c->mu; nothing is in flight)
     drop_decode_graphs(c);
     return LASR_OK;
@@ -2135,77 +2142,13 @@ int lasr_fetch_many_aligned(lasr_ctx* c, const int* slots, int n, int32_t* token
     return fetch_many(c, slots, n, tokens, frames, logps, cap, n_new);
 }
 
-// ---------------------------------------------------------------------------- contextual biasing
+// ---------------------------------------------------------------------------- contextual biasing, greedy and beam
 int lasr_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
                       int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_bonus, int32_t* depth,
                       int* n_nodes, int* n_edges) {
     return lasr_bias::compile(tokens, n_tokens, weights, k, vocab, blank, cap_nodes, cap_edges, edge_off, edge_tok, edge_next, edge_bonus,
                               depth, n_nodes, n_edges);
 }
-// Greedy decode: with a graph attached the decode launches run k_select<.., BIAS = true> at one frame per iteration, and every
-// row carries its automaton node beside its predictor state (DecState::bias_node; null = off, the default).  Like the record
-// switches this changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  The
-// graph is checked on the host before anything changes.
-int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_bonus) {
-    if (!c) return LASR_EINVAL;
-    if (c->W > 1)
-        return fail(c, LASR_EINVAL, "lasr_set_bias serves greedy decode (beam = 1); beam search has lasr_set_beam_bias, where the bonus is "
-                                    "part of the ranking score");
-    if (n_nodes == 0 && !c->ds.bias_node) return LASR_OK;       // (off already: also fine while steps are in flight)
-    if (n_nodes != 0) {
-        if (c->lm.on)
-            return fail(c, LASR_ESTATE, "lasr_set_bias refuses an attached LM (the fuser re-picks on standardised scores, in which a bonus in "
-                                        "log-prob units has no defined place)");
-        const char* bad = lasr_bias::validate(n_nodes, edge_off, edge_tok, edge_next, edge_bonus, c->d.vocab, c->d.blank);
-        if (bad) return fail(c, LASR_EINVAL, "lasr_set_bias: %s", bad);
-    }
-    RC(toggle_prologue(c, "slot %d has %d unfetched token(s): fetch them before the switch"));
-    int* tab = nullptr;
-    size_t E = 0;
-    if (n_nodes) {
-        E = (size_t)edge_off[n_nodes];
-        std::vector<int> img((size_t)n_nodes + 1 + 3 * E);
-        std::copy(edge_off, edge_off + n_nodes + 1, img.begin());
-        if (E) {
-            std::copy(edge_tok, edge_tok + E, img.begin() + n_nodes + 1);
-            std::copy(edge_next, edge_next + E, img.begin() + n_nodes + 1 + E);
-            memcpy(img.data() + n_nodes + 1 + 2 * E, edge_bonus, sizeof(float) * E);
-        }
-        RC(upload(c, &tab, (const int*)img.data(), img.size()));
-        if (!c->bias_node_dev) RC(dalloc(c, &c->bias_node_dev, (size_t)c->M));
-        HIPCHK(c, hipMemset(c->bias_node_dev, 0, sizeof(int) * (size_t)c->M));      // every slot starts over at the root
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    dfree(c, c->bias_tab);
-    c->bias_tab = tab;
-    c->bias_nodes = n_nodes;
-    DecState& s = c->ds;
-    s.bias_node = n_nodes ? c->bias_node_dev : nullptr;
-    s.bias_off = tab;
-    s.bias_tok = tab ? tab + n_nodes + 1 : nullptr;
-    s.bias_next = tab ? tab + n_nodes + 1 + E : nullptr;
-    s.bias_bonus = tab ? (const float*)(tab + n_nodes + 1 + 2 * E) : nullptr;
-    return LASR_OK;
-}
-
-int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes) {
-    if (!c) return LASR_EINVAL;
-    if (!c->ds.bias_node) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
-    RC(flush_lazy(c));
-    RC(require_idle(c));
-    RC(check_slots(c, slots, n, true));
-    if (n == 0) return LASR_OK;
-    if (!nodes) return fail(c, LASR_EINVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
-    std::vector<int> all((size_t)c->M);
-    HIPCHK(c, hipMemcpy(all.data(), c->bias_node_dev, sizeof(int) * all.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) nodes[i] = all[slots[i]];
-    return LASR_OK;
-}
-
-// ---------------------------------------------------------------------------- contextual biasing in the beam
 int lasr_beam_bias_compile(const int32_t* tokens, const int32_t* n_tokens, const float* weights, int k, int vocab, int blank, int cap_nodes,
                            int cap_edges, int32_t* edge_off, int32_t* edge_tok, int32_t* edge_next, float* edge_gain, float* node_back,
                            int32_t* depth, int* n_nodes, int* n_edges) {
@@ -2216,60 +2159,102 @@ int lasr_bias_walk(int n_nodes, const int32_t* edge_off, const int32_t* edge_tok
                    const float* node_back, int blank, const int32_t* tokens, int n, int start, int* end_node, double* total, float* gains) {
     return lasr_bias::walk(n_nodes, edge_off, edge_tok, edge_next, edge_gain, node_back, blank, tokens, n, start, end_node, total, gains);
 }
-// Beam search: with a graph attached the selection rounds run k_beam_select_rw<.., BIAS = true>, and every hypothesis slot carries
-// its automaton node through the parent indirection (BeamState::bias_node; null = off, the default).  Like lasr_set_beam_merge this
-// changes which kernel the decode launches run, so the engine must be idle and the cached groups are dropped.  The graph is checked
-// on the host before anything changes.  The scores stay what they are, at switch-on and at switch-off.
+// Attaching, replacing or detaching (n_nodes = 0) a graph, behind the setter's width refusal.  beam: the beam form -- edge_val is
+// the gain and node_back the fifth column; else the greedy form -- edge_val is the bonus, node_back is not looked at.  `fn`: the
+// entry point's name in the texts.  With a graph attached the decode launches run k_select<.., BIAS = true> at one frame per
+// iteration (greedy) or k_beam_select_rw<.., BIAS = true> (beam), and every row carries its automaton node beside its predictor
+// state (greedy) or through the parent indirection (beam).  Like the record switches this changes which kernel the decode launches
+// run, so the engine must be idle and the cached groups are dropped.  The graph is checked on the host before anything changes; a
+// failure behind the upload frees the new block and leaves the context as it was.  A beam's scores stay what they are, at
+// switch-on and at switch-off.
+static int bias_attach(lasr_ctx* c, bool beam, const char* fn, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok,
+                       const int32_t* edge_next, const float* edge_val, const float* node_back) {
+    if (n_nodes == 0 && !bias_on(c)) return LASR_OK;            // (off already: also fine while steps are in flight)
+    if (n_nodes != 0) {
+        if (c->lm.on)
+            return fail(c, LASR_ESTATE, beam ? "lasr_set_beam_bias refuses an attached LM (the combination with LM fusion is not served)"
+                                             : "lasr_set_bias refuses an attached LM (the fuser re-picks on standardised scores, in which a "
+                                               "bonus in log-prob units has no defined place)");
+        const char* bad = lasr_bias::validate_form(beam, n_nodes, edge_off, edge_tok, edge_next, edge_val, node_back, c->d.vocab, c->d.blank);
+        if (bad) return fail(c, LASR_EINVAL, "%s: %s", fn, bad);
+    }
+    RC(toggle_prologue(c, beam ? "slot %d holds a result that was not fetched: fetch it before the switch"
+                               : "slot %d has %d unfetched token(s): fetch them before the switch"));
+    lasr_ctx::Bias nb;
+    if (n_nodes) {
+        const std::vector<int32_t> img = lasr_bias::pack_block(n_nodes, edge_off, edge_tok, edge_next, edge_val, beam ? node_back : nullptr);
+        nb.n_nodes = n_nodes; nb.n_edges = (size_t)edge_off[n_nodes]; nb.has_back = beam;
+        const size_t rows = beam ? (size_t)c->Md : (size_t)c->M;
+        auto stage = [&]() -> int {
+            RC(upload(c, &nb.block, (const int*)img.data(), img.size()));
+            if (!c->bias.node) RC(dalloc(c, &c->bias.node, rows));
+            HIPCHK(c, hipMemset(c->bias.node, 0, sizeof(int) * rows));      // every slot starts over at the root
+            return LASR_OK;
+        };
+        const int rc = stage();
+        if (rc) { dfree(c, nb.block); return rc; }
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    dfree(c, c->bias.block);
+    nb.node = c->bias.node;
+    c->bias = nb;
+    if (!beam) {            // (a beam's view is beam_state()'s)
+        c->ds.bias = BiasEdges{};
+        if (n_nodes) { c->ds.bias.node = nb.node; (void)lasr_bias::view_block(nb.block, nb.n_nodes, nb.n_edges, false, c->ds.bias); }
+    }
+    return LASR_OK;
+}
+
+int lasr_set_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const float* edge_bonus) {
+    if (!c) return LASR_EINVAL;
+    if (c->W > 1)
+        return fail(c, LASR_EINVAL, "lasr_set_bias serves greedy decode (beam = 1); beam search has lasr_set_beam_bias, where the bonus is "
+                                    "part of the ranking score");
+    return bias_attach(c, false, "lasr_set_bias", n_nodes, edge_off, edge_tok, edge_next, edge_bonus, nullptr);
+}
 int lasr_set_beam_bias(lasr_ctx* c, int n_nodes, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next,
                        const float* edge_gain, const float* node_back) {
     if (!c) return LASR_EINVAL;
     if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_set_beam_bias serves beam search (beam > 1); greedy decode has lasr_set_bias");
-    if (n_nodes == 0 && !c->bbias_nodes) return LASR_OK;        // (off already: also fine while steps are in flight)
-    if (n_nodes != 0) {
-        if (c->lm.on) return fail(c, LASR_ESTATE, "lasr_set_beam_bias refuses an attached LM (the combination with LM fusion is not served)");
-        const char* bad = lasr_bias::validate_beam(n_nodes, edge_off, edge_tok, edge_next, edge_gain, node_back, c->d.vocab, c->d.blank);
-        if (bad) return fail(c, LASR_EINVAL, "lasr_set_beam_bias: %s", bad);
-    }
-    RC(toggle_prologue(c, "slot %d holds a result that was not fetched: fetch it before the switch"));
-    int* tab = nullptr;
-    size_t E = 0;
-    if (n_nodes) {
-        E = (size_t)edge_off[n_nodes];
-        std::vector<int> img((size_t)n_nodes + 1 + 3 * E + (size_t)n_nodes);
-        std::copy(edge_off, edge_off + n_nodes + 1, img.begin());
-        if (E) {
-            std::copy(edge_tok, edge_tok + E, img.begin() + n_nodes + 1);
-            std::copy(edge_next, edge_next + E, img.begin() + n_nodes + 1 + E);
-            memcpy(img.data() + n_nodes + 1 + 2 * E, edge_gain, sizeof(float) * E);
-        }
-        memcpy(img.data() + n_nodes + 1 + 3 * E, node_back, sizeof(float) * (size_t)n_nodes);
-        RC(upload(c, &tab, (const int*)img.data(), img.size()));
-        if (!c->b_bias_node) RC(dalloc(c, &c->b_bias_node, (size_t)c->Md));
-        HIPCHK(c, hipMemset(c->b_bias_node, 0, sizeof(int) * (size_t)c->Md));      // every slot starts over at the root
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    dfree(c, c->bbias_tab);
-    c->bbias_tab = tab;
-    c->bbias_nodes = n_nodes;
-    c->bbias_edges = E;
+    return bias_attach(c, true, "lasr_set_beam_bias", n_nodes, edge_off, edge_tok, edge_next, edge_gain, node_back);
+}
+
+// n words of the node row from row `at`, on the host (the caller has drained the streams)
+static int read_bias_nodes(lasr_ctx* c, size_t at, int* out, size_t n) {
+    HIPCHK(c, hipMemcpy(out, c->bias.node + at, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return LASR_OK;
+}
+// the start nodes an op-level call was handed: inside the attached graph
+static int check_bias_nodes(lasr_ctx* c, const int32_t* node, size_t n) {
+    for (size_t r = 0; r < n; ++r)
+        if (node[r] < 0 || node[r] >= c->bias.n_nodes) return fail(c, LASR_EINVAL, "row %zu: node %d outside [0, %d)", r, node[r], c->bias.n_nodes);
+    return LASR_OK;
+}
+
+int lasr_bias_state(lasr_ctx* c, const int* slots, int n, int32_t* nodes) {
+    if (!c) return LASR_EINVAL;
+    if (c->W > 1 || !bias_on(c)) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
+    RC(drain(c));
+    RC(check_slots(c, slots, n, true));
+    if (n == 0) return LASR_OK;
+    if (!nodes) return fail(c, LASR_EINVAL, "null argument");
+    std::vector<int> all((size_t)c->M);
+    RC(read_bias_nodes(c, 0, all.data(), all.size()));
+    for (int i = 0; i < n; ++i) nodes[i] = all[slots[i]];
     return LASR_OK;
 }
 
 int lasr_beam_bias_state(lasr_ctx* c, int slot, int32_t* nodes) {
     if (!c) return LASR_EINVAL;
     if (c->W <= 1) return fail(c, LASR_EINVAL, "lasr_beam_bias_state serves beam search (beam > 1); greedy decode has lasr_bias_state");
-    if (!c->bbias_nodes) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
-    RC(flush_lazy(c));
-    RC(require_idle(c));
+    if (!bias_on(c)) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
+    RC(drain(c));
     RC(open_slot(c, slot));
     if (!nodes) return fail(c, LASR_EINVAL, "null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
-    std::vector<int> nd((size_t)c->W), al((size_t)c->W);
-    HIPCHK(c, hipMemcpy(nd.data(), c->b_bias_node + (size_t)slot * c->W, sizeof(int) * nd.size(), hipMemcpyDeviceToHost));
+    std::vector<int> al((size_t)c->W);
+    RC(read_bias_nodes(c, (size_t)slot * c->W, nodes, al.size()));
     HIPCHK(c, hipMemcpy(al.data(), c->b_alive + (size_t)slot * c->W, sizeof(int) * al.size(), hipMemcpyDeviceToHost));
-    for (int j = 0; j < c->W; ++j) nodes[j] = al[j] ? nd[j] : -1;
+    for (int j = 0; j < c->W; ++j) if (!al[j]) nodes[j] = -1;      // (a dead slot has no node)
     return LASR_OK;
 }
 
@@ -2283,11 +2268,10 @@ int lasr_beam_bias_round(lasr_ctx* c, const float* logits, int n, const double* 
     if (!logits || !score || !alive || !inB || !node || !rounds || !parent || !token || !emit || !score_out || !alive_out || !inB_out ||
         !node_out || !term || n < 1 || n > c->d.max_streams || max_iters < 1)
         return fail(c, LASR_EINVAL, "bad argument");
-    if (!c->bbias_nodes) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
+    if (!bias_on(c)) return fail(c, LASR_ESTATE, "beam biasing is off: call lasr_set_beam_bias first");
     const int W = c->W, M = c->M;
     const size_t Md = (size_t)c->Md, nW = (size_t)n * W;
-    for (size_t r = 0; r < nW; ++r)
-        if (node[r] < 0 || node[r] >= c->bbias_nodes) return fail(c, LASR_EINVAL, "row %zu: node %d outside [0, %d)", r, node[r], c->bbias_nodes);
+    RC(check_bias_nodes(c, node, nW));
     for (int q = 0; q < n; ++q)
         if (rounds[q] < 0) return fail(c, LASR_EINVAL, "stream %d: %d rounds done", q, rounds[q]);
     RC(flush_lazy(c));
@@ -2296,9 +2280,9 @@ int lasr_beam_bias_round(lasr_ctx* c, const float* logits, int n, const double* 
     // scratch: [Md] doubles (score), then int rows: alive, inB, node, token, emit, parent, trellis [Md each], rec [2 Md],
     // iters, t_idx, T_row [M each], unfinished [1]
     const size_t n_int = 9 * Md + 3 * (size_t)M + 1;
-    if (!c->bbias_round_dev) RC(dalloc(c, &c->bbias_round_dev, Md + (n_int + 1) / 2));
+    if (!c->bias_round_dev) RC(dalloc(c, &c->bias_round_dev, Md + (n_int + 1) / 2));
     static_assert(sizeof(BeamRec) == 2 * sizeof(int), "BeamRec is two words");
-    double* d_sc = c->bbias_round_dev;
+    double* d_sc = c->bias_round_dev;
     int* d_i = (int*)(d_sc + Md);
     std::vector<double> h_sc(Md, -INFINITY);
     std::vector<int> h_i(n_int, 0);
@@ -2309,7 +2293,7 @@ int lasr_beam_bias_round(lasr_ctx* c, const float* logits, int n, const double* 
     HIPCHK(c, hipMemcpyAsync(d_i, h_i.data(), sizeof(int) * n_int, hipMemcpyHostToDevice, c->stream));
     DecView v = sync_view(c, c->la_sync);
     BeamState b = beam_state(c, v, false, max_iters);
-    b.score = d_sc; b.alive = d_i; b.inB = d_i + Md; b.bias_node = d_i + 2 * Md; b.token = d_i + 3 * Md; b.emit = d_i + 4 * Md;
+    b.score = d_sc; b.alive = d_i; b.inB = d_i + Md; b.bias.node = d_i + 2 * Md; b.token = d_i + 3 * Md; b.emit = d_i + 4 * Md;
     b.parent = d_i + 5 * Md; b.trellis = d_i + 6 * Md; b.rec = (BeamRec*)(d_i + 7 * Md);
     b.iters = d_i + 9 * Md; b.t_idx = d_i + 9 * Md + M; b.T_row = d_i + 9 * Md + 2 * (size_t)M; b.unfinished = d_i + 9 * Md + 3 * (size_t)M;
     b.seq_hash = nullptr; b.seq_len = nullptr; b.dbg = nullptr;
@@ -2533,9 +2517,8 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
                        (const int*)nullptr, (const int*)nullptr, c->ja, J, c->M, c->MTj, 1 << 30, c->bf, 1, c->M, 1);
     launch_logits(c, v, logits, B, false);
     if (logp_max && argmax) {
-        DecState s = c->ds;
-        s.bias_node = nullptr;                       // the joint's own argmax, whatever graph is attached (lasr_bias_pick is the biased one)
-        launch_select<true>(c->stream, B, logits, V, c->d.blank, 1, nullptr, s, 0, logp_max, argmax, 1, c->M);
+        // the joint's own argmax, whatever graph is attached (lasr_bias_pick is the biased one)
+        launch_select<true>(c->stream, B, logits, V, c->d.blank, 1, nullptr, c->ds, 0, logp_max, argmax, 1, c->M, false);
     }
     HIPCHK(c, hipGetLastError());
     return LASR_OK;
@@ -2545,17 +2528,16 @@ int lasr_joint(lasr_ctx* c, const float* h_pred, const float* h_enc, int B, floa
 // its own -- no slot's state is read or written
 int lasr_bias_pick(lasr_ctx* c, const float* logits, const int32_t* node, int B, int32_t* tok, int32_t* next, float* logp) {
     if (!c || !logits || !node || !tok || !next || !logp || B < 1 || B > c->d.max_streams) return c ? fail(c, LASR_EINVAL, "bad argument") : LASR_EINVAL;
-    if (!c->ds.bias_node) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
-    for (int r = 0; r < B; ++r)
-        if (node[r] < 0 || node[r] >= c->bias_nodes) return fail(c, LASR_EINVAL, "row %d: node %d outside [0, %d)", r, node[r], c->bias_nodes);
+    if (c->W > 1 || !bias_on(c)) return fail(c, LASR_ESTATE, "biasing is off: call lasr_set_bias first");
+    RC(check_bias_nodes(c, node, (size_t)B));
     HIPCHK(c, hipSetDevice(c->device));
     const size_t M = (size_t)c->M;
     if (!c->bias_pick_dev) RC(dalloc(c, &c->bias_pick_dev, 3 * M));      // [node -> next | tok | log p]
     int* nd = c->bias_pick_dev;
     HIPCHK(c, hipMemcpyAsync(nd, node, sizeof(int) * (size_t)B, hipMemcpyHostToDevice, c->stream));
     DecState s = c->ds;
-    s.bias_node = nd;
-    launch_select<true>(c->stream, B, logits, c->d.vocab, c->d.blank, 1, nullptr, s, 0, (float*)(nd + 2 * M), nd + M, 1, c->M);
+    s.bias.node = nd;
+    launch_select<true>(c->stream, B, logits, c->d.vocab, c->d.blank, 1, nullptr, s, 0, (float*)(nd + 2 * M), nd + M, 1, c->M, true);
     HIPCHK(c, hipGetLastError());
     std::vector<int> out(3 * M);
     HIPCHK(c, hipMemcpyAsync(out.data(), nd, sizeof(int) * 3 * M, hipMemcpyDeviceToHost, c->stream));
@@ -2740,11 +2722,10 @@ static int lm_side_setup(lasr_ctx* c) {
 static int lm_attach_begin(lasr_ctx* c, const lasr_lm_desc* d, const float* weights, size_t n_weights, bool q8) {
     if (!c) return LASR_EINVAL;
     if (c->lm.on) return fail(c, LASR_ESTATE, "an LM is already attached");
-    if (c->ds.bias_node)
-        return fail(c, LASR_ESTATE, "a bias graph is set (the fuser re-picks on standardised scores, in which a bonus in log-prob units has "
-                                    "no defined place): lasr_set_bias(c, 0, ...) first");
-    if (c->bbias_nodes)
-        return fail(c, LASR_ESTATE, "a beam bias graph is set (the combination with LM fusion is not served): lasr_set_beam_bias(c, 0, ...) first");
+    if (bias_on(c))
+        return fail(c, LASR_ESTATE, c->W > 1 ? "a beam bias graph is set (the combination with LM fusion is not served): lasr_set_beam_bias(c, 0, ...) first"
+                                             : "a bias graph is set (the fuser re-picks on standardised scores, in which a bonus in log-prob units "
+                                               "has no defined place): lasr_set_bias(c, 0, ...) first");
     if (c->beam_merge == 1) return fail(c, LASR_ESTATE, "beam merging is on in the mode that refuses an LM (lasr_set_beam_merge(c, 0) or (c, LASR_BEAM_MERGE_LM) first)");
     if (q8 && c->W > 1) return fail(c, LASR_ESTATE, "LM shallow fusion is implemented for greedy decoding (beam = 1)");
     if (!d || !weights || n_weights != lasr_lm_weight_count(d) || n_weights == 0)
@@ -3114,10 +3095,7 @@ int lasr_trace_read(lasr_ctx* c, double* us, int* tags, int cap, int* n) {
 // n_pend, T_row_fix, t_idx, token, emit.  *rows / *cols (optional) describe the matrix; cap = floats `out` holds.
 int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, int* rows, int* cols) {
     if (!c || !out) return LASR_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    RC(flush_lazy(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->stream_dec) HIPCHK(c, hipStreamSynchronize(c->stream_dec));
+    RC(drain(c, false));
     const lasr_model_desc& d = c->d;
     const int M = c->M, H = d.hidden, F = d.feat, J = d.joint;
     int R = M, K = 0;

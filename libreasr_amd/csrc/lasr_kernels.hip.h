@@ -279,6 +279,16 @@ __device__ __forceinline__ void cont_arrive(const ContRound& s, ContSlot rd, int
     }
 }
 
+// a phrase automaton as the selection kernels read it (lasr_bias.hip.h): every row's node, and the CSR edge lists over the nodes,
+// tokens ascending per node.  One device block holds the four columns (lasr_bias::block_layout is the one place that knows its layout)
+struct BiasEdges {
+    int* node;                 // [rows] the row's node
+    const int* off;            // [n_nodes + 1]
+    const int* tok;            // [n_edges]
+    const int* next;           // [n_edges] in [1, n_nodes)
+    const float* val;          // [n_edges] greedy: the bonus; beam: the gain
+};
+
 // per-step decode state
 struct DecState : ContRound {
     int* t_idx;        // [M] current encoder frame of the row inside this step
@@ -305,13 +315,9 @@ struct DecState : ContRound {
     const int* lm_valid; // [M] the LM has advanced at least once since the last LM reset
     float lm_alpha, lm_theta, lm_min;
     unsigned long long* dbg;   // LASR_DBG_TIMING: phase stamps of k_select's workgroup 0 (wall clock, 10 ns ticks)
-    // contextual biasing (lasr_set_bias): the row's node in the phrase automaton and the automaton's edge lists (CSR
-    // over the nodes, tokens ascending per node).  bias_node == nullptr: off -- the launcher then picks the BIAS = false kernels
-    int* bias_node;            // [M]
-    const int* bias_off;       // [n_nodes + 1]
-    const int* bias_tok;       // [n_edges]
-    const int* bias_next;      // [n_edges] in [1, n_nodes)
-    const float* bias_bonus;   // [n_edges] finite, >= 0
+    // contextual biasing (lasr_set_bias): the row's node in the phrase automaton ([M]) and the automaton's edge lists;
+    // val = the bonus, finite and >= 0.  bias.node == nullptr: off -- the decode launches then run the BIAS = false kernels
+    BiasEdges bias;
 };
 
 // block-wide sum over 256 threads (4 waves); every thread gets the result
@@ -585,7 +591,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
     const bool dbgt = !PLAIN && s.dbg && r == 0 && tid == 0;
     const unsigned long long t_entry = dbgt ? wall_clock64() : 0ull;
     int bias_v = 0;                                               // the row's automaton node (in flight with the logits)
-    if constexpr (BIAS) bias_v = s.bias_node[r];
+    if constexpr (BIAS) bias_v = s.bias.node[r];
     float zv[LAT][KEEP];
 #pragma unroll
     for (int k = 0; k < LAT; ++k) {
@@ -672,15 +678,15 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
         // of (z[arg], arg) and the listed edges: the workgroup strides over deg(v) edges, never over V again.  The edge tokens of a
         // node are distinct, so (s, tok) identifies its edge and the reduction need not carry it: the thread that scanned the
         // winning edge knows.  The same scan notes the edge of arg itself (where the row goes if the unbiased choice stands).
-        const int e0 = s.bias_off[bias_v], e1 = s.bias_off[bias_v + 1];
+        const int e0 = s.bias.off[bias_v], e1 = s.bias.off[bias_v + 1];
         const float* z = logits + (size_t)r * V;
         float eb = -INFINITY, my_z = 0.f;
         int ea = 0x7fffffff, my_next = 0, arg_next = 0;
         for (int e = e0 + tid; e < e1; e += 256) {
-            const int tk = s.bias_tok[e];
+            const int tk = s.bias.tok[e];
             const float zt = z[tk];                  // (the row this workgroup has just streamed)
-            const float sc = __fadd_rn(zt, s.bias_bonus[e]);
-            const int nx = s.bias_next[e];
+            const float sc = __fadd_rn(zt, s.bias.val[e]);
+            const int nx = s.bias.next[e];
             if (tk == arg[0]) arg_next = nx;
             if (amax_before(sc, tk, eb, ea)) { eb = sc; ea = tk; my_z = zt; my_next = nx; }
         }
@@ -708,7 +714,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
     if (PLAIN) {
         if (tid == 0) {
             out_logp[r] = logp[0]; out_arg[r] = arg[0];
-            if constexpr (BIAS) s.bias_node[r] = node_next;
+            if constexpr (BIAS) s.bias.node[r] = node_next;
         }
         return;
     }
@@ -767,7 +773,7 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ logits
                 }
                 n0 += 1;
                 s.token[r] = tok;
-                if constexpr (BIAS) s.bias_node[r] = node_next;      // beside the token: the same release orders both
+                if constexpr (BIAS) s.bias.node[r] = node_next;      // beside the token: the same release orders both
             }
             frame_done = it >= max_iters;           // per-frame symbol cap
         }
@@ -1014,13 +1020,9 @@ struct BeamState : ContRound {
     int* seq_len;                   // [Md]
     // contextual biasing in the beam (lasr_set_beam_bias): every slot's node in the phrase automaton and the graph in
     // beam form -- CSR edge lists (tokens ascending per node) with a signed gain per edge, and per node the gain of every non-blank
-    // token that is not listed.  bias_node == nullptr: off (k_beam_select_rw<WT, REC, MERGE, false> never looks).  (At the end of
-    // the struct: the kernel-argument offsets of everything above are what they were.)
-    int* bias_node;            // [Md]
-    const int* bias_off;       // [n_nodes + 1]
-    const int* bias_tok;       // [n_edges]
-    const int* bias_next;      // [n_edges] in [1, n_nodes)
-    const float* bias_gain;    // [n_edges] |gain| <= 1000
+    // token that is not listed.  bias.node ([Md]) == nullptr: off (k_beam_select_rw<WT, REC, MERGE, false> never looks).  (At the end
+    // of the struct: the kernel-argument offsets of everything above are what they were.)
+    BiasEdges bias;            // val = the gain, |gain| <= 1000
     const float* bias_back;    // [n_nodes] in [-1000, 0]
 };
 
@@ -1093,7 +1095,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     const bool inA = alb && !ibb;                    // wave-uniform
     // (BIAS) the row's node, read in front of the barrier behind which wave 0 stores the new ones
     int node_b = 0;
-    if constexpr (BIAS) { if (in) node_b = s.bias_node[r0 + b]; }
+    if constexpr (BIAS) { if (in) node_b = s.bias.node[r0 + b]; }
     if (dbg) s.dbg[1] = wall_clock64();
     if (!inA) {
 #pragma unroll
@@ -1161,7 +1163,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
                 }
             // the wave's own LDS traffic is issued in order; the fence + wave barrier keep the compiler from moving it
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            for (int e = s.bias_off[node_b] + lane, ee = s.bias_off[node_b + 1]; e < ee; e += 64) gr[s.bias_tok[e]] = s.bias_gain[e];
+            for (int e = s.bias.off[node_b] + lane, ee = s.bias.off[node_b + 1]; e < ee; e += 64) gr[s.bias.tok[e]] = s.bias.val[e];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
             for (int vw = 0; vw < VW; ++vw)
@@ -1247,7 +1249,7 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
     if constexpr (MERGE) { if (lane < W) { id_hash = s.seq_hash[r0 + lane]; id_len = s.seq_len[r0 + lane]; } }
     // (BIAS) likewise this lane's own slot's node (wave 0's row is slot 0: lane j reads slot j's)
     int my_node = 0;
-    if constexpr (BIAS) { if (lane < W) my_node = s.bias_node[r0 + lane]; }
+    if constexpr (BIAS) { if (lane < W) my_node = s.bias.node[r0 + lane]; }
     // ---- the ordered top-W of the WT x WT candidate table, by wave 0 (round 6; one thread before: W passes over W list heads + W
     // slots of bookkeeping = 3.1 us of 7.6 at W = 4, 7.6 of 13.3 at W = 8).  Lane l holds candidate (row l / WT, position l % WT); its
     // rank = the number of candidates that come before it in the total order (score descending, ordinal ascending: ordinals are
@@ -1295,12 +1297,12 @@ __global__ __launch_bounds__(64 * WT) void k_beam_select_rw(const float* __restr
         for (int j = 0; j < WT; ++j) { const int nj = __builtin_amdgcn_readlane(my_node, j); if (pb == j) pn = nj; }
         int nn = live ? pn : 0;
         if (live && k > 0 && k - 1 != s.blank) {
-            int lo = s.bias_off[pn], hi = s.bias_off[pn + 1];
+            int lo = s.bias.off[pn], hi = s.bias.off[pn + 1];
             const int end = hi;
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (s.bias_tok[mid] < k - 1) lo = mid + 1; else hi = mid; }
-            nn = lo < end && s.bias_tok[lo] == k - 1 ? s.bias_next[lo] : 0;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (s.bias.tok[mid] < k - 1) lo = mid + 1; else hi = mid; }
+            nn = lo < end && s.bias.tok[lo] == k - 1 ? s.bias.next[lo] : 0;
         }
-        if (slot) s.bias_node[r0 + lane] = nn;      // (a plain store: the round's release orders it like seq_hash)
+        if (slot) s.bias.node[r0 + lane] = nn;      // (a plain store: the round's release orders it like seq_hash)
     }
     if (slot) {
         const int r = r0 + lane;

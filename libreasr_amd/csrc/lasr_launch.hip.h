@@ -21,13 +21,13 @@ struct DecView {
     int pred_par, lm_par;           // advanced by the helpers
 };
 // synchronous / offline protocols and the op-level entry points: the caller's stream, whole-step buffers
-// (a bias graph attached: one frame per iteration on every protocol)
+// (a bias graph attached: one frame per iteration on every protocol; a beam's la is 1 with or without)
 inline DecView sync_view(lasr_ctx* c, int la) {
-    return DecView{c->stream, c->pe_sync, 1 << 30, c->ds.t_idx, c->T_row_fix, c->ds.bias_node ? 1 : la, true, nullptr, c->pred_par, c->lm.par};
+    return DecView{c->stream, c->pe_sync, 1 << 30, c->ds.t_idx, c->T_row_fix, bias_on(c) ? 1 : la, true, nullptr, c->pred_par, c->lm.par};
 }
 // continuous loop of the pipelined protocol: the decode stream, per-row rings and cursors
 inline DecView cont_view(lasr_ctx* c) {
-    return DecView{c->stream_dec, c->pe_ring, lasr_ctx::RING, c->c_cur, c->c_avail, c->ds.bias_node ? 1 : c->la_stream, false, nullptr, c->pred_par, c->lm.par};
+    return DecView{c->stream_dec, c->pe_ring, lasr_ctx::RING, c->c_cur, c->c_avail, bias_on(c) ? 1 : c->la_stream, false, nullptr, c->pred_par, c->lm.par};
 }
 // s_setprio of a GEMM by the stream it runs on: the decode loop's two streams against everything else
 inline int gemm_prio(const lasr_ctx* c, hipStream_t st) {
@@ -173,9 +173,9 @@ inline bool keep16(int V) {
 // k_select with the compile-time lookahead bound that covers `la` (1, 2, 4) and 8 or 16 register slots per thread and frame
 template <bool PLAIN>
 inline void launch_select(hipStream_t st, int rows, const float* logits, int V, int blank, int max_iters, const int* T_row,
-                          const DecState& s, int iter_slot, float* out_logp, int* out_arg, int la, int M) {
+                          const DecState& s, int iter_slot, float* out_logp, int* out_arg, int la, int M, bool bias) {
     with_const<8, 16>(V <= 2048 && !s.lmz ? 8 : 16, [&](auto keep) {      // (the LM re-pick keeps the whole row in registers: 16 slots)
-        if (s.bias_node) {           // a graph is attached (lasr_set_bias): the BIAS kernels, one frame per launch (the views say la = 1)
+        if (bias) {                  // bias_on(c) in the decode loops (lasr_set_bias): the BIAS kernels, one frame per launch (the views say la = 1)
             hipLaunchKernelGGL((k_select<PLAIN, 1, decltype(keep)::value, true>), dim3(rows), dim3(256), 0, st, logits, V, blank, max_iters,
                                T_row, s, iter_slot, out_logp, out_arg, 1, M);
             return;

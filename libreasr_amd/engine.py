@@ -28,82 +28,70 @@ def _ptr(x):
 
 
 class BiasGraph:
-    """The phrase automaton of contextual biasing in lasr_set_bias' layout (CSR edge lists, int32 / float32 host arrays);
-    depth: the trie depth per node."""
+    """The phrase automaton of contextual biasing as CSR edge lists (int32 / float32 host arrays).  Greedy form (lasr_set_bias'
+    layout): edge_val is the bonus per edge, finite and >= 0, and node_back is None.  Beam form (lasr_set_beam_bias' layout):
+    edge_val is a signed gain per edge, and node_back holds, per node, the gain of every non-blank token that is not listed
+    (<= 0).  edge_bonus and edge_gain both name the one float column.  depth: the trie depth per node."""
 
-    def __init__(self, edge_off, edge_tok, edge_next, edge_bonus, depth=None):
+    def __init__(self, edge_off, edge_tok, edge_next, edge_val, depth=None, node_back=None):
         self.edge_off = np.ascontiguousarray(edge_off, dtype=np.int32)
         self.edge_tok = np.ascontiguousarray(edge_tok, dtype=np.int32)
         self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32)
-        self.edge_bonus = np.ascontiguousarray(edge_bonus, dtype=np.float32)
+        self.edge_val = np.ascontiguousarray(edge_val, dtype=np.float32)
+        self.node_back = None if node_back is None else np.ascontiguousarray(node_back, dtype=np.float32)
         self.depth = None if depth is None else np.ascontiguousarray(depth, dtype=np.int32)
         self.n_nodes = int(self.edge_off.size) - 1
         self.n_edges = int(self.edge_tok.size)
+
+    edge_bonus = edge_gain = property(lambda self: self.edge_val)
+
+
+class BeamBiasGraph(BiasGraph):
+    """BiasGraph in beam form, with the columns in lasr_set_beam_bias' order"""
+
+    def __init__(self, edge_off, edge_tok, edge_next, edge_gain, node_back, depth=None):
+        super().__init__(edge_off, edge_tok, edge_next, edge_gain, depth, node_back)
+
+
+def _bias_compile(lib, beam, phrases, weights, vocab, blank):
+    """lasr_bias_compile / lasr_beam_bias_compile (beam; no context, no GPU): sized by a first call with no room, filled by the
+    second"""
+    name = "beam_bias_compile" if beam else "bias_compile"
+    fn = getattr(lib, "lasr_" + name)
+    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
+    k = len(toks)
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if k < 1 or w.size != k:
+        raise ValueError(name + ": at least one phrase and one weight per phrase")
+    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
+    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
+    nn, ne = C.c_int(0), C.c_int(0)
+
+    def call(cap_nodes, cap_edges, n, e, with_depth):      # room for n nodes and e edges (the back column in beam form only)
+        off, etok, enxt, val = np.zeros(n + 1, np.int32), np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.float32)
+        back, dep = np.zeros(max(n, 1), np.float32), np.zeros(n, np.int32) if with_depth else None
+        cols = [off, etok, enxt, val] + ([back] if beam else []) + [dep]
+        rc = fn(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), cap_nodes, cap_edges, *[_ptr(x) for x in cols], C.byref(nn),
+                C.byref(ne))
+        return rc, off, etok, enxt, val, back, dep
+
+    rc = call(0, 0, 0, 1, False)[0]
+    if rc != N.LASR_EFULL:
+        raise N.LasrError(rc, "lasr_" + name + ": phrases of >= 1 ids in [0, vocab) other than blank, weights finite and >= 0"
+                              + (", no gain beyond 1000" if beam else ""))
+    n, e = nn.value, ne.value
+    rc, off, etok, enxt, val, back, dep = call(n, e, n, max(e, 1), True)
+    if rc != 0:
+        raise N.LasrError(rc, "lasr_" + name)
+    return BeamBiasGraph(off, etok[:e], enxt[:e], val[:e], back, dep) if beam else BiasGraph(off, etok[:e], enxt[:e], val[:e], dep)
 
 
 def bias_compile(lib, phrases, weights, vocab, blank):
-    """lasr_bias_compile (no context, no GPU): sized by a first call with no room, filled by the second"""
-    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
-    k = len(toks)
-    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
-    if k < 1 or w.size != k:
-        raise ValueError("bias_compile: at least one phrase and one weight per phrase")
-    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
-    nn, ne = C.c_int(0), C.c_int(0)
-    one = [np.zeros(1, np.int32) for _ in range(3)] + [np.zeros(1, np.float32)]
-    rc = lib.lasr_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), 0, 0, _ptr(one[0]), _ptr(one[1]), _ptr(one[2]),
-                               _ptr(one[3]), None, C.byref(nn), C.byref(ne))
-    if rc != N.LASR_EFULL:
-        raise N.LasrError(rc, "lasr_bias_compile: phrases of >= 1 ids in [0, vocab) other than blank, weights finite and >= 0")
-    off, dep = np.zeros(nn.value + 1, np.int32), np.zeros(nn.value, np.int32)
-    etok, enxt, ebon = np.zeros(max(ne.value, 1), np.int32), np.zeros(max(ne.value, 1), np.int32), np.zeros(max(ne.value, 1), np.float32)
-    rc = lib.lasr_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), nn.value, ne.value, _ptr(off), _ptr(etok),
-                               _ptr(enxt), _ptr(ebon), _ptr(dep), C.byref(nn), C.byref(ne))
-    if rc != 0:
-        raise N.LasrError(rc, "lasr_bias_compile")
-    return BiasGraph(off, etok[:ne.value], enxt[:ne.value], ebon[:ne.value], dep)
-
-
-class BeamBiasGraph:
-    """The phrase automaton in beam form, lasr_set_beam_bias' layout: BiasGraph's CSR lists with a signed gain per edge and, per
-    node, the gain of every non-blank token that is not listed (node_back <= 0)."""
-
-    def __init__(self, edge_off, edge_tok, edge_next, edge_gain, node_back, depth=None):
-        self.edge_off = np.ascontiguousarray(edge_off, dtype=np.int32)
-        self.edge_tok = np.ascontiguousarray(edge_tok, dtype=np.int32)
-        self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32)
-        self.edge_gain = np.ascontiguousarray(edge_gain, dtype=np.float32)
-        self.node_back = np.ascontiguousarray(node_back, dtype=np.float32)
-        self.depth = None if depth is None else np.ascontiguousarray(depth, dtype=np.int32)
-        self.n_nodes = int(self.edge_off.size) - 1
-        self.n_edges = int(self.edge_tok.size)
+    return _bias_compile(lib, False, phrases, weights, vocab, blank)
 
 
 def beam_bias_compile(lib, phrases, weights, vocab, blank):
-    """lasr_beam_bias_compile (no context, no GPU): sized by a first call with no room, filled by the second"""
-    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
-    k = len(toks)
-    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
-    if k < 1 or w.size != k:
-        raise ValueError("beam_bias_compile: at least one phrase and one weight per phrase")
-    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
-    nn, ne = C.c_int(0), C.c_int(0)
-    one = [np.zeros(1, np.int32) for _ in range(3)] + [np.zeros(1, np.float32), np.zeros(1, np.float32)]
-    rc = lib.lasr_beam_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), 0, 0, _ptr(one[0]), _ptr(one[1]),
-                                    _ptr(one[2]), _ptr(one[3]), _ptr(one[4]), None, C.byref(nn), C.byref(ne))
-    if rc != N.LASR_EFULL:
-        raise N.LasrError(rc, "lasr_beam_bias_compile: phrases of >= 1 ids in [0, vocab) other than blank, weights finite and >= 0, "
-                              "no gain beyond 1000")
-    e = max(ne.value, 1)
-    off, dep, back = np.zeros(nn.value + 1, np.int32), np.zeros(nn.value, np.int32), np.zeros(nn.value, np.float32)
-    etok, enxt, egain = np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.float32)
-    rc = lib.lasr_beam_bias_compile(_ptr(tok), _ptr(nt), _ptr(w), k, int(vocab), int(blank), nn.value, ne.value, _ptr(off), _ptr(etok),
-                                    _ptr(enxt), _ptr(egain), _ptr(back), _ptr(dep), C.byref(nn), C.byref(ne))
-    if rc != 0:
-        raise N.LasrError(rc, "lasr_beam_bias_compile")
-    return BeamBiasGraph(off, etok[:ne.value], enxt[:ne.value], egain[:ne.value], back, dep)
+    return _bias_compile(lib, True, phrases, weights, vocab, blank)
 
 
 def bias_walk(lib, graph, tokens, blank, start=0):
@@ -814,6 +802,8 @@ class Engine:
         if graph is None:
             self._chk(self.lib.lasr_set_bias(self.ctx, 0, None, None, None, None))
             return
+        if graph.node_back is not None:
+            raise ValueError("set_bias: a graph in beam form (it carries node_back); bias_compile gives the greedy form")
         self._chk(self.lib.lasr_set_bias(self.ctx, int(graph.n_nodes), _ptr(graph.edge_off), _ptr(graph.edge_tok),
                                          _ptr(graph.edge_next), _ptr(graph.edge_bonus)))
 
@@ -850,6 +840,8 @@ class Engine:
             self._chk(self.lib.lasr_set_beam_bias(self.ctx, 0, None, None, None, None, None))
             self.beam_bias = None
             return
+        if graph.node_back is None:
+            raise ValueError("set_beam_bias: a graph in greedy form (no node_back); beam_bias_compile gives the beam form")
         self._chk(self.lib.lasr_set_beam_bias(self.ctx, int(graph.n_nodes), _ptr(graph.edge_off), _ptr(graph.edge_tok),
                                               _ptr(graph.edge_next), _ptr(graph.edge_gain), _ptr(graph.node_back)))
         self.beam_bias = graph

@@ -253,6 +253,23 @@ def test_beam_bias_round_is_exact(V, W):
         assert np.all((got2["token"][tail] >= -1) & (got2["token"][tail] < V)) and np.all((got2["node"][tail] >= 0) & (got2["node"][tail] < g.n_nodes))
         assert np.all((got2["parent"][tail] >= 0) & (got2["parent"][tail] < W))
         assert code(eng.beam_bias_round, torch.from_numpy(z).cuda(), score, alive, inB, node + g.n_nodes, rounds, MAX_ITERS) == N.LASR_EINVAL
+        # a live graph replaced by one of another size, and back: a hand-made graph of two nodes and one edge (A gains 1.5 at the
+        # root and leads to node 1, where every other non-blank token hands it back) on the same logits, rows off the root in node 1
+        small = BB.Graph([0, 1, 1], [A_], [1], [1.5], [0.0, -1.5])
+        node1 = np.minimum(node, 1).astype(np.int32)
+        want1 = round_ref(z, score, alive, inB, node1, rounds, small, W, MAX_ITERS)
+        assert want1["gap"] >= 0.25, want1["gap"]      # (f32 log-softmax plus a gain errs by some 1e-5 at these sizes: every decision is clear)
+        assert set(want1["node"].tolist()) == {0, 1} and want1["emit"].any()
+        eng.set_beam_bias(native(small))
+        got1 = eng.beam_bias_round(torch.from_numpy(z).cuda(), score, alive, inB, node1, rounds, MAX_ITERS)
+        for q, name in enumerate(names):
+            check_round(got1, want1, list(range(q * W, (q + 1) * W)), (V, W, name, "two nodes"))
+        assert code(eng.beam_bias_round, torch.from_numpy(z).cuda(), score, alive, inB, node, rounds, MAX_ITERS) == N.LASR_EINVAL      # (g's nodes)
+        eng.set_beam_bias(native(g))
+        again = eng.beam_bias_round(torch.from_numpy(z).cuda(), score, alive, inB, node, rounds, MAX_ITERS)
+        assert sorted(again) == sorted(got) and len(got) == 8
+        for k in got:
+            assert again[k].dtype == got[k].dtype and again[k].tobytes() == got[k].tobytes(), (V, W, k)
     finally:
         eng.close()
 
@@ -621,6 +638,9 @@ def test_refusals_change_nothing():
         }
         for what, g in bad.items():
             assert code(eng.set_beam_bias, native(g)) == N.LASR_EINVAL, what
+        from libreasr_amd.engine import BiasGraph
+        with pytest.raises(ValueError):                                           # a graph of the greedy form: no node_back
+            eng.set_beam_bias(BiasGraph(good.off, good.tok, good.nxt, np.abs(good.gain), good.depth))
         # nothing changed: biasing is still off, and the context decodes as its twin
         assert code(eng.beam_bias_state, 0) == N.LASR_ESTATE
         assert all_paths(eng) == twin("f32")

@@ -481,6 +481,9 @@ def test_refusals_change_nothing():
         from libreasr_amd.engine import BiasGraph
         big = BiasGraph(np.zeros(65538, np.int32), [], [], [])
         assert big.n_nodes == 65537 and code(eng.set_bias, big) == N.LASR_EINVAL
+        from libreasr_amd.engine import BeamBiasGraph
+        with pytest.raises(ValueError):                                           # a graph of the beam form: it carries node_back
+            eng.set_bias(BeamBiasGraph(good.off, good.tok, good.nxt, good.bonus, np.zeros(good.n_nodes, np.float32), good.depth))
         # nothing changed: biasing is still off, and the context decodes as its twin
         assert code(eng.bias_state, [0]) == N.LASR_ESTATE
         assert all_paths(eng) == twin("f32")
