@@ -5,6 +5,8 @@ device path (PCM in, token ids / text out; features never leave the GPU).
     text = asr.transcribe(pcm)                       # 1-D float32 16 kHz, or path to a .flac / .wav (any rate: resampled on the GPU)
     for text_so_far in asr.stream(chunks): ...       # 80 ms float32 chunks (bytes / arrays / tensors)
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -50,6 +52,27 @@ class LibreASR:
         if sr != self.engine.desc.sample_rate:
             pcm = self.engine.resample(torch.as_tensor(np.ascontiguousarray(pcm)[None]).to(self.engine.device), sr)[0]
         return pcm
+
+    @contextlib.contextmanager
+    def _open(self, n):
+        """n open slots for the body of the `with`; every slot that was opened is closed on any exit, a failed open() included"""
+        slots = []
+        try:
+            for _ in range(n):
+                slots.append(self.engine.open())
+            yield slots
+        finally:
+            for s in slots:
+                self.engine.close_slot(s)
+
+    def _groups(self, ys, call):
+        """the candidates in groups of up to max_streams, each with one open slot per candidate: yields call(slots, group), the
+        group's slots closed again"""
+        g = self.engine.max_streams
+        for i in range(0, len(ys), g):
+            with self._open(len(ys[i:i + g])) as slots:
+                res = call(slots, ys[i:i + g])
+            yield res
 
     def _want_alignment(self):
         """Turns the engine's per-token records on (greedy decode only; a no-op when they are on already)."""
@@ -117,8 +140,7 @@ class LibreASR:
             self._want_alignment()
         if nbest is not None:
             self._want_nbest(nbest)
-        slots = [self.engine.open() for _ in batch]
-        try:
+        with self._open(len(batch)) as slots:
             self.engine.transcribe_pcm(slots, [self._utterance(a) for a in batch])
             if nbest is not None:
                 out = [self._nbest(s, nbest, bonus=getattr(self.engine, "beam_bias", None) is not None) for s in slots]
@@ -126,9 +148,6 @@ class LibreASR:
                 out = [self._aligned(*self.engine.fetch_aligned(s)[:3]) for s in slots]
             else:
                 ids = [self.engine.fetch(s)[0] for s in slots]
-        finally:
-            for s in slots:
-                self.engine.close_slot(s)
         if not return_alignment and nbest is None:
             out = ids if return_ids else [self.lang.denumericalize(i) for i in ids]
         return out if isinstance(audio, (list, tuple)) else out[0]
@@ -215,12 +234,8 @@ class LibreASR:
         ys = [self._ids(t) for t in (transcript if many else [transcript])]
         if len(ys) != len(batch):
             raise ValueError("one transcript per utterance")
-        slots = [self.engine.open() for _ in batch]
-        try:
+        with self._open(len(batch)) as slots:
             res = call(slots, [self._utterance(a) for a in batch], ys)
-        finally:
-            for s in slots:
-                self.engine.close_slot(s)
         out = [{"score": r["loglik"], "viterbi": r["viterbi"], "tokens": self._aligned(y, r["frames"], r["logps"])} for r, y in zip(res, ys)]
         if posteriors:
             for o, r in zip(out, res):
@@ -270,16 +285,8 @@ class LibreASR:
         `rescore` encodes it once per group and shares the candidates' common prefixes."""
         ys = [self._ids(t) for t in candidates]
         pcm = self._utterance(audio)
-        out, g = [], self.engine.max_streams
-        for i in range(0, len(ys), g):
-            part = ys[i:i + g]
-            slots = [self.engine.open() for _ in part]
-            try:
-                out += [r["loglik"] for r in self.engine.align_pcm(slots, [pcm] * len(part), part, viterbi=False)]
-            finally:
-                for s in slots:
-                    self.engine.close_slot(s)
-        return out
+        call = lambda slots, part: self.engine.align_pcm(slots, [pcm] * len(part), part, viterbi=False)
+        return [r["loglik"] for res in self._groups(ys, call) for r in res]
 
     def rescore(self, audio, candidates, viterbi=False):
         """log P(candidate | audio), summed over all alignments, of every candidate transcript of ONE utterance, in the candidates'
@@ -288,15 +295,8 @@ class LibreASR:
         viterbi=True: -> (scores, best-alignment log-probabilities)."""
         ys = [self._ids(t) for t in candidates]
         pcm = self._utterance(audio)
-        out, vit, g = [], [], self.engine.max_streams
-        for i in range(0, len(ys), g):
-            part = ys[i:i + g]
-            slots = [self.engine.open() for _ in part]
-            try:
-                r = self.engine.score_pcm([slots], [pcm], [part], viterbi=viterbi)[0]
-            finally:
-                for s in slots:
-                    self.engine.close_slot(s)
+        out, vit = [], []
+        for r in self._groups(ys, lambda slots, part: self.engine.score_pcm([slots], [pcm], [part], viterbi=viterbi)[0]):
             out += [float(v) for v in r["loglik"]]
             if viterbi:
                 vit += [float(v) for v in r["viterbi"]]
@@ -307,16 +307,8 @@ class LibreASR:
         order: one engine call per group of up to max_streams candidates.  start=None: the LM reads the labels themselves and the
         first one has no term; start=id: the LM reads that token first and every label has a term."""
         ys = [self._ids(t) for t in candidates]
-        out, g = [], self.engine.max_streams
-        for i in range(0, len(ys), g):
-            part = ys[i:i + g]
-            slots = [self.engine.open() for _ in part]
-            try:
-                out += [float(r["total"]) for r in self.engine.lm_score(slots, part, start=start)]
-            finally:
-                for s in slots:
-                    self.engine.close_slot(s)
-        return out
+        call = lambda slots, part: self.engine.lm_score(slots, part, start=start)
+        return [float(r["total"]) for res in self._groups(ys, call) for r in res]
 
     def rescore_lm(self, audio, candidates, lm_weight, length_bonus=0.0, start=None):
         """Second-pass combination of ONE utterance's candidates: score = log P(candidate | audio) + lm_weight * log P_LM(candidate)
@@ -325,16 +317,11 @@ class LibreASR:
         "best": index of the largest score (a tie takes the lowest index), "order": indices by score descending, ties by index}."""
         ys = [self._ids(t) for t in candidates]
         pcm = self._utterance(audio)
-        am, lm, g = [], [], self.engine.max_streams
-        for i in range(0, len(ys), g):
-            part = ys[i:i + g]
-            slots = [self.engine.open() for _ in part]
-            try:
-                am += [float(v) for v in self.engine.score_pcm([slots], [pcm], [part])[0]["loglik"]]
-                lm += [float(r["total"]) for r in self.engine.lm_score(slots, part, start=start)]
-            finally:
-                for s in slots:
-                    self.engine.close_slot(s)
+        am, lm = [], []
+        call = lambda slots, part: (self.engine.score_pcm([slots], [pcm], [part])[0]["loglik"], self.engine.lm_score(slots, part, start=start))
+        for a, l in self._groups(ys, call):
+            am += [float(v) for v in a]
+            lm += [float(r["total"]) for r in l]
         score = [float(np.float64(a) + np.float64(lm_weight) * np.float64(l) + np.float64(length_bonus) * np.float64(len(y)))
                  for a, l, y in zip(am, lm, ys)]
         order = sorted(range(len(score)), key=lambda j: (-score[j], j))

@@ -27,6 +27,17 @@ def _ptr(x):
     raise TypeError(type(x))
 
 
+def _ragged(lists, dtype=np.int32, pad=0):
+    """lists of numbers (token lists, candidates, windows, parents) -> (their concatenation with room for `pad` more, int32 counts)"""
+    parts = [np.asarray(x, dtype=dtype).reshape(-1) for x in lists]
+    return np.ascontiguousarray(np.concatenate(parts + [np.zeros(pad, dtype)])), np.array([x.size for x in parts], dtype=np.int32)
+
+
+def _rows(x, oc, t, w):
+    """a copy of t rows of w cells from cell oc of a flat lattice output"""
+    return x[oc:oc + t * w].reshape(t, w).copy()
+
+
 class BiasGraph:
     """The phrase automaton of contextual biasing as CSR edge lists (int32 / float32 host arrays).  Greedy form (lasr_set_bias'
     layout): edge_val is the bonus per edge, finite and >= 0, and node_back is None.  Beam form (lasr_set_beam_bias' layout):
@@ -58,13 +69,11 @@ def _bias_compile(lib, beam, phrases, weights, vocab, blank):
     second"""
     name = "beam_bias_compile" if beam else "bias_compile"
     fn = getattr(lib, "lasr_" + name)
-    toks = [np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases]
-    k = len(toks)
+    tok, nt = _ragged(phrases, pad=1)
+    k = int(nt.size)
     w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
     if k < 1 or w.size != k:
         raise ValueError(name + ": at least one phrase and one weight per phrase")
-    nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-    tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(1, np.int32)]))
     nn, ne = C.c_int(0), C.c_int(0)
 
     def call(cap_nodes, cap_edges, n, e, with_depth):      # room for n nodes and e edges (the back column in beam form only)
@@ -439,128 +448,128 @@ class Engine:
                 for i in range(min(k, nh.value))]
 
     # ------------------------------------------------------------------ offline
-    def transcribe_pcm(self, slots, pcm_list):
-        """pcm_list: list of 1-D float32 arrays/tensors (one utterance per slot)."""
-        a, p, n = self._slots(slots)
-        assert len(pcm_list) == n
+    def _cat_pcm(self, pcm_list):
+        """-> (all utterances concatenated: one device tensor if every one is, else one host array; int64 sample counts)"""
         if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
             cat = torch.cat([x.reshape(-1).float() for x in pcm_list]).contiguous()
         else:   # mixed / host inputs: gather on the host, one H2D copy inside the library
             cat = np.ascontiguousarray(np.concatenate([
                 np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
                 for x in pcm_list]))
-        ns = np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
-        self._chk(self.lib.lasr_transcribe_pcm(self.ctx, p, n, _ptr(cat), ns.ctypes.data_as(C.c_void_p)))
+        return cat, np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64)
+
+    def _cat_feats(self, feats_list):
+        """-> (all [T', feat] blocks concatenated, device or host as _cat_pcm; int32 frame counts)"""
+        F = self.desc.feat
+        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
+            arrs = [x.reshape(-1, F).float() for x in feats_list]
+            cat = torch.cat(arrs).contiguous()
+        else:
+            arrs = [np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
+            cat = np.ascontiguousarray(np.concatenate(arrs))
+        return cat, np.array([x.shape[0] for x in arrs], dtype=np.int32)
+
+    def _cat(self, pcm, slots, audio):
+        """the audio of an offline call, one utterance per listed slot -> (slot pointer, n, _cat_pcm's or _cat_feats' pair)"""
+        a, p, n = self._slots(slots)
+        assert len(audio) == n
+        return p, n, (self._cat_pcm(audio) if pcm else self._cat_feats(audio))
+
+    def transcribe_pcm(self, slots, pcm_list):
+        """pcm_list: list of 1-D float32 arrays/tensors (one utterance per slot)."""
+        p, n, (cat, ns) = self._cat(True, slots, pcm_list)
+        self._chk(self.lib.lasr_transcribe_pcm(self.ctx, p, n, _ptr(cat), _ptr(ns)))
 
     def transcribe_feats(self, slots, feats_list):
         """feats_list: list of [T', feat] float32 arrays/tensors."""
-        a, p, n = self._slots(slots)
-        assert len(feats_list) == n
-        F = self.desc.feat
-        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
-            cat = torch.cat([x.reshape(-1, F).float() for x in feats_list]).contiguous()
-            nf = [x.reshape(-1, F).shape[0] for x in feats_list]
-        else:
-            arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
-            cat = np.ascontiguousarray(np.concatenate(arrs))
-            nf = [a_.shape[0] for a_ in arrs]
-        nf = np.ascontiguousarray(np.array(nf, dtype=np.int32))
-        self._chk(self.lib.lasr_transcribe_feats(self.ctx, p, n, _ptr(cat), nf.ctypes.data_as(C.c_void_p)))
+        p, n, (cat, nf) = self._cat(False, slots, feats_list)
+        self._chk(self.lib.lasr_transcribe_feats(self.ctx, p, n, _ptr(cat), _ptr(nf)))
+
+    # ------------------------------------------------------------------ the optional outputs of the lattice calls, and utterance i of them
+    @staticmethod
+    def _vit_buffers(n, n_tok, viterbi, logps=True):
+        """host outputs of the alignment pass, in the order of the C arguments: viterbi [n], frames and (logps=True) logps [n_tok];
+        None each without the pass"""
+        k = max(n_tok, 1)
+        return (np.zeros(n, dtype=np.float64) if viterbi else None, np.zeros(k, dtype=np.int32) if viterbi else None,
+                np.zeros(k, dtype=np.float32) if viterbi and logps else None)
+
+    @staticmethod
+    def _vit_slice(vit, i, u, o):
+        """one utterance of the alignment pass' outputs: entry i, u labels from o"""
+        v, fr, lp = vit
+        if v is None:
+            return {}
+        r = dict(viterbi=float(v[i]), frames=fr[o:o + u].copy())
+        return r if lp is None else dict(r, logps=lp[o:o + u].copy())
+
+    @staticmethod
+    def _post_buffers(cells, n_tok):
+        """host outputs of a posterior call, in the order of the C arguments: occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak"""
+        k = max(n_tok, 1)
+        return (np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32), np.zeros(k, dtype=np.float64),
+                np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64))
+
+    @staticmethod
+    def _post_slice(post, t, w, u, oc, o):
+        """one utterance of the posterior outputs: t rows of w cells from oc, u labels from o"""
+        ob, oe, mean, var, pf, peak = post
+        return dict(occ_blank=_rows(ob, oc, t, w), occ_emit=_rows(oe, oc, t, w),
+                    tok_mean=mean[o:o + u].copy(), tok_var=var[o:o + u].copy(), tok_peak_frame=pf[o:o + u].copy(), tok_peak=peak[o:o + u].copy())
+
+    @staticmethod
+    def _walk(U, T=None, W=None):
+        """per utterance (i, u labels, t frames, w cells per row -- None: the full lattice's u + 1 --, and where its labels, cells and
+        frames start in the concatenated outputs: o, oc, ot)"""
+        o = oc = ot = 0
+        for i, u in enumerate(U):
+            u, t = int(u), 0 if T is None else int(T[i])
+            w = u + 1 if W is None else int(W[i])
+            yield i, u, t, w, o, oc, ot
+            o, oc, ot = o + u, oc + t * w, ot + t
+
+    def _align_frames(self, lens, pcm):
+        d = self.desc
+        if not pcm:
+            return [int(v) for v in lens]
+        return [((1 + int(v) // d.hop) - d.n_stack) // d.stride + 1 for v in lens]
 
     # ------------------------------------------------------------------ forced alignment / transcript scoring
-    def _align(self, fn, slots, cat, lens, token_lists, lattice, viterbi, posteriors=False, band=None, max_passes=1, windows=None):
+    def _align(self, pcm, slots, audio, token_lists, lattice, viterbi, posteriors=False, band=None, max_passes=1, windows=None):
+        """lasr_align_[band_][post_]{pcm,feats}, by name from (band, posteriors, pcm).  A row of utterance i has U_i + 1 cells, with a
+        band w_i (band layout); the band adds "lo", "width", "passes", "touch", posteriors add lattice_post's six fields."""
+        p, n, (cat, lens) = self._cat(pcm, slots, audio)
+        assert len(token_lists) == n
+        tok, U = _ragged(token_lists)
+        Ts = self._align_frames(lens, pcm)      # what the library derives from the audio: the encoder frames of the utterance
+        W = [int(u) + 1 if band is None or t == 1 else min(int(band), int(u) + 1) for t, u in zip(Ts, U)]
+        cells, n_tok = max(sum(t * w for t, w in zip(Ts, W)), 1), int(tok.size)
+        loglik = np.zeros(n, dtype=np.float64)
+        vit = self._vit_buffers(n, n_tok, viterbi)
+        b, e = (np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32)) if lattice else (None, None)
+        args, outs = [self.ctx, p, n, _ptr(cat), _ptr(lens), _ptr(tok), _ptr(U)], [loglik, *vit, b, e]
         if band is not None:
-            if posteriors:
-                raise ValueError("posteriors with a band: use align_band_post_pcm / align_band_post_feats")
-            return self._align_band(fn is self.lib.lasr_align_pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows)
-        a, p, n = self._slots(slots)
-        assert len(token_lists) == n
-        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
-        U = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
-        loglik = np.zeros(n, dtype=np.float64)
-        vit = np.zeros(n, dtype=np.float64) if viterbi else None
-        fr = np.zeros(max(int(tok.size), 1), dtype=np.int32) if viterbi else None
-        lp = np.zeros(max(int(tok.size), 1), dtype=np.float32) if viterbi else None
-        b = e = None
-        pcm = fn is self.lib.lasr_align_pcm
-        if lattice or posteriors:      # T_i is what the library derives from the audio: the encoder frames of the utterance
-            Ts = self._align_frames(lens, pcm)
-            cells = int(sum(int(t) * (int(u) + 1) for t, u in zip(Ts, U)))
-        if lattice:
-            b, e = np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32)
-        args = (self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p),
-                U.ctypes.data_as(C.c_void_p), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e))
-        if posteriors:
-            post = self._post_buffers(cells, int(tok.size))
-            fn = self.lib.lasr_align_post_pcm if pcm else self.lib.lasr_align_post_feats
-            args += tuple(_ptr(x) for x in post)
-        self._chk(fn(*args))
-        out, o, oc = [], 0, 0
-        for i in range(n):
-            u = int(U[i])
-            r = {"loglik": float(loglik[i])}
-            if viterbi:
-                r.update(viterbi=float(vit[i]), frames=fr[o:o + u].copy(), logps=lp[o:o + u].copy())
+            lo_in = None
+            if windows is not None:
+                assert len(windows) == n
+                lo_in = _ragged(windows)[0]
+                if lo_in.size != sum(Ts):
+                    raise N.LasrError(N.LASR_EINVAL, "windows: one start per encoder frame of every utterance")
+            lo, passes, touch = np.zeros(max(sum(Ts), 1), dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+            args += [int(band), int(max_passes), _ptr(lo_in)]
+            outs += [lo, passes, touch]
+        post = self._post_buffers(cells, n_tok) if posteriors else ()
+        fn = getattr(self.lib, "lasr_align_" + ("band_" if band is not None else "") + ("post_" if posteriors else "") + ("pcm" if pcm else "feats"))
+        self._chk(fn(*args, *[_ptr(x) for x in (*outs, *post)]))
+        out = []
+        for i, u, t, w, o, oc, ot in self._walk(U, Ts, W):
+            r = {"loglik": float(loglik[i]), **self._vit_slice(vit, i, u, o)}
             if lattice:
-                t = int(Ts[i])
-                r.update(blank_lp=b[oc:oc + t * (u + 1)].reshape(t, u + 1).copy(), emit_lp=e[oc:oc + t * (u + 1)].reshape(t, u + 1).copy())
+                r.update(blank_lp=_rows(b, oc, t, w), emit_lp=_rows(e, oc, t, w))
+            if band is not None:
+                r.update(lo=lo[ot:ot + t].copy(), width=w, passes=int(passes[i]), touch=int(touch[i]))
             if posteriors:
-                r.update(self._post_slice(post, int(Ts[i]), u, oc, o))
-            if lattice or posteriors:
-                oc += int(Ts[i]) * (u + 1)
-            o += u
-            out.append(r)
-        return out
-
-    def _align_band(self, pcm, slots, cat, lens, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=False):
-        """lasr_align_band_pcm / _feats: _align's dicts with the lattice arrays [T, w] in band layout, and "lo", "width", "passes", "touch";
-        posteriors (lasr_align_band_post_pcm / _feats): also lattice_post's six fields, the occupancies [T, w] in band layout."""
-        a, p, n = self._slots(slots)
-        assert len(token_lists) == n
-        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
-        U = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
-        Ts = self._align_frames(lens, pcm)
-        W = [int(u) + 1 if int(t) == 1 else min(int(band), int(u) + 1) for t, u in zip(Ts, U)]
-        cells = int(sum(int(t) * w for t, w in zip(Ts, W)))
-        loglik = np.zeros(n, dtype=np.float64)
-        vit = np.zeros(n, dtype=np.float64) if viterbi else None
-        fr = np.zeros(max(int(tok.size), 1), dtype=np.int32) if viterbi else None
-        lp = np.zeros(max(int(tok.size), 1), dtype=np.float32) if viterbi else None
-        b = np.zeros(max(cells, 1), dtype=np.float32) if lattice else None
-        e = np.zeros(max(cells, 1), dtype=np.float32) if lattice else None
-        lo_in = None
-        if windows is not None:
-            assert len(windows) == n
-            lo_in = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in windows]))
-            if lo_in.size != sum(Ts):
-                raise N.LasrError(N.LASR_EINVAL, "windows: one start per encoder frame of every utterance")
-        lo = np.zeros(max(int(sum(Ts)), 1), dtype=np.int32)
-        passes, touch = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
-        fn = self.lib.lasr_align_band_pcm if pcm else self.lib.lasr_align_band_feats
-        args = (self.ctx, p, n, _ptr(cat), lens.ctypes.data_as(C.c_void_p), tok.ctypes.data_as(C.c_void_p), U.ctypes.data_as(C.c_void_p),
-                int(band), int(max_passes), _ptr(lo_in), _ptr(loglik), _ptr(vit), _ptr(fr), _ptr(lp), _ptr(b), _ptr(e), _ptr(lo),
-                _ptr(passes), _ptr(touch))
-        if posteriors:
-            post = self._post_buffers(max(cells, 1), int(tok.size))
-            fn = self.lib.lasr_align_band_post_pcm if pcm else self.lib.lasr_align_band_post_feats
-            args += tuple(_ptr(x) for x in post)
-        self._chk(fn(*args))
-        out, o, oc, ot = [], 0, 0, 0
-        for i in range(n):
-            u, t, w = int(U[i]), int(Ts[i]), W[i]
-            r = {"loglik": float(loglik[i])}
-            if viterbi:
-                r.update(viterbi=float(vit[i]), frames=fr[o:o + u].copy(), logps=lp[o:o + u].copy())
-            if lattice:
-                r.update(blank_lp=b[oc:oc + t * w].reshape(t, w).copy(), emit_lp=e[oc:oc + t * w].reshape(t, w).copy())
-            r.update(lo=lo[ot:ot + t].copy(), width=w, passes=int(passes[i]), touch=int(touch[i]))
-            if posteriors:
-                r.update(self._post_slice(post, t, u, oc, o, w))
-            o += u
-            oc += t * w
-            ot += t
+                r.update(self._post_slice(post, t, w, u, oc, o))
             out.append(r)
         return out
 
@@ -589,76 +598,48 @@ class Engine:
         """The banded dynamic programme alone (lasr_lattice_band_dp) on caller-supplied band lattices: blank / emit = lists of
         [T_i, w_i] float32 arrays in band layout (row t holds the columns lo_i[t] .. lo_i[t] + w_i - 1), lo = their window starts,
         U = their label counts.  -> per lattice {"loglik", "viterbi", "frames"}."""
-        n, b, e, T, Us, W, los = self._band_lattices(blank, emit, lo, U)
-        loglik = np.zeros(n, dtype=np.float64)
-        vit = np.zeros(n, dtype=np.float64) if viterbi else None
-        fr = np.zeros(max(int(Us.sum()), 1), dtype=np.int32) if viterbi else None
-        self._chk(self.lib.lasr_lattice_band_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Us), _ptr(W), _ptr(los), n, _ptr(loglik), _ptr(vit),
-                                                _ptr(fr)))
-        out, o = [], 0
-        for i in range(n):
-            r = {"loglik": float(loglik[i])}
-            if viterbi:
-                r.update(viterbi=float(vit[i]), frames=fr[o:o + int(Us[i])].copy())
-            o += int(Us[i])
-            out.append(r)
-        return out
+        return self._lattice_dp(self.lib.lasr_lattice_band_dp, self._band_lattices(blank, emit, lo, U), viterbi)
 
     @staticmethod
-    def _band_lattices(blank, emit, lo, U):
-        """the inputs of lattice_band_dp / lattice_band_post concatenated -> (n, b, e, T, U, W, lo)"""
+    def _lattices(blank, emit):
+        """caller-supplied lattices concatenated -> (n, b, e, T, their second dimension)"""
         n = len(blank)
-        assert n == len(emit) == len(lo) == len(U) and n >= 1
-        bs = [np.asarray(x, dtype=np.float32) for x in blank]
-        es = [np.asarray(x, dtype=np.float32) for x in emit]
+        assert n == len(emit) and n >= 1
+        bs, es = ([np.asarray(x, dtype=np.float32) for x in xs] for xs in (blank, emit))
         assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
-        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
-        W = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
-        Us = np.ascontiguousarray(np.array([int(u) for u in U], dtype=np.int32))
-        los = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int32).reshape(-1) for x in lo]))
+        b, e = (np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in xs])) for xs in (bs, es))
+        return n, b, e, np.array([x.shape[0] for x in bs], dtype=np.int32), np.array([x.shape[1] for x in bs], dtype=np.int32)
+
+    def _band_lattices(self, blank, emit, lo, U):
+        """the inputs of lattice_band_dp / lattice_band_post in the order of the C arguments: (b, e, T, U, W, lo)"""
+        n, b, e, T, W = self._lattices(blank, emit)
+        assert n == len(lo) == len(U)
+        los = _ragged(lo)[0]
         assert los.size == int(T.sum())
-        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
-        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
-        return n, b, e, T, Us, W, los
+        return b, e, T, np.array([int(u) for u in U], dtype=np.int32), W, los
+
+    def _lattice_dp(self, fn, ins, viterbi):
+        """lasr_lattice_dp / lasr_lattice_band_dp on ins = (b, e, T, U, ..), the C inputs in order"""
+        U = ins[3]
+        n = int(U.size)
+        loglik, vit = np.zeros(n, dtype=np.float64), self._vit_buffers(n, int(U.sum()), viterbi, logps=False)
+        self._chk(fn(self.ctx, *[_ptr(x) for x in ins], n, _ptr(loglik), _ptr(vit[0]), _ptr(vit[1])))
+        return [{"loglik": float(loglik[i]), **self._vit_slice(vit, i, u, o)} for i, u, _, _, o, _, _ in self._walk(U)]
+
+    def _lattice_post(self, fn, ins, W):
+        """lasr_lattice_post / lasr_lattice_band_post on ins = (b, e, T, U, ..), the C inputs in order; W: the cells per row"""
+        b, _, T, U = ins[:4]
+        n = int(U.size)
+        loglik, bwd, post = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64), self._post_buffers(int(b.size), int(U.sum()))
+        self._chk(fn(self.ctx, *[_ptr(x) for x in ins], n, _ptr(loglik), _ptr(bwd), *[_ptr(x) for x in post]))
+        return [{"loglik": float(loglik[i]), "loglik_bwd": float(bwd[i]), **self._post_slice(post, t, w, u, oc, o)}
+                for i, u, t, w, o, oc, _ in self._walk(U, T, W)]
 
     def lattice_band_post(self, blank, emit, lo, U):
         """Banded forward-backward alone (lasr_lattice_band_post) on caller-supplied band lattices, the arguments of lattice_band_dp.
         -> per lattice lattice_post's dict, "occ_blank" / "occ_emit" [T, w] float32 in band layout."""
-        n, b, e, T, Us, W, los = self._band_lattices(blank, emit, lo, U)
-        loglik, bwd = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
-        post = self._post_buffers(int(b.size), int(Us.sum()))
-        self._chk(self.lib.lasr_lattice_band_post(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Us), _ptr(W), _ptr(los), n, _ptr(loglik), _ptr(bwd),
-                                                  *[_ptr(x) for x in post]))
-        out, o, oc = [], 0, 0
-        for i in range(n):
-            t, u, w = int(T[i]), int(Us[i]), int(W[i])
-            r = {"loglik": float(loglik[i]), "loglik_bwd": float(bwd[i])}
-            r.update(self._post_slice(post, t, u, oc, o, w))
-            o += u
-            oc += t * w
-            out.append(r)
-        return out
-
-    @staticmethod
-    def _post_buffers(cells, n_tok):
-        """host outputs of a posterior call, in the order of the C arguments: occ_blank, occ_emit, tok_mean, tok_var, tok_peak_frame, tok_peak"""
-        k = max(n_tok, 1)
-        return (np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32), np.zeros(k, dtype=np.float64),
-                np.zeros(k, dtype=np.float64), np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.float64))
-
-    @staticmethod
-    def _post_slice(post, t, u, oc, o, row=None):
-        """one utterance of the posterior outputs: t rows of `row` cells from oc (None: the full lattice's u + 1), u labels from o"""
-        ob, oe, mean, var, pf, peak = post
-        row = u + 1 if row is None else row
-        return dict(occ_blank=ob[oc:oc + t * row].reshape(t, row).copy(), occ_emit=oe[oc:oc + t * row].reshape(t, row).copy(),
-                    tok_mean=mean[o:o + u].copy(), tok_var=var[o:o + u].copy(), tok_peak_frame=pf[o:o + u].copy(), tok_peak=peak[o:o + u].copy())
-
-    def _align_frames(self, lens, pcm):
-        d = self.desc
-        if not pcm:
-            return [int(v) for v in lens]
-        return [((1 + int(v) // d.hop) - d.n_stack) // d.stride + 1 for v in lens]
+        ins = self._band_lattices(blank, emit, lo, U)
+        return self._lattice_post(self.lib.lasr_lattice_band_post, ins, ins[4])
 
     def align_pcm(self, slots, pcm_list, token_lists, lattice=False, viterbi=True, posteriors=False, band=None, max_passes=1, windows=None):
         """Teacher-forced RNN-T lattice of every (utterance, transcript) pair (lasr_align_pcm): pcm_list as for transcribe_pcm,
@@ -673,39 +654,17 @@ class Engine:
         passes; transcripts of up to 32767 labels.  The dict then also has "lo" int32 [T] (the last pass's windows), "width",
         "passes" and "touch", and the lattice arrays are [T, w] in band layout (row t holds the columns lo[t] .. lo[t] + w - 1).
         band with posteriors=True raises ValueError: the band's posteriors are align_band_post_pcm's."""
-        cat, ns = self._align_pcm_input(slots, pcm_list)
-        return self._align(self.lib.lasr_align_pcm, slots, cat, ns, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
+        return self._align_public(True, slots, pcm_list, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
 
-    def _align_pcm_input(self, slots, pcm_list):
-        """the utterances of an align_*_pcm call concatenated (host, or device when all of them are) and their sample counts"""
-        a, p, n = self._slots(slots)
-        assert len(pcm_list) == n
-        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
-            cat = torch.cat([x.reshape(-1).float() for x in pcm_list]).contiguous()
-        else:
-            cat = np.ascontiguousarray(np.concatenate([
-                np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
-                for x in pcm_list]))
-        return cat, np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
+    def _align_public(self, pcm, slots, audio, token_lists, lattice, viterbi, posteriors, band, max_passes, windows):
+        """align_pcm / align_feats: _align, minus the combination that has methods of its own"""
+        if band is not None and posteriors:
+            raise ValueError("posteriors with a band: use align_band_post_pcm / align_band_post_feats")
+        return self._align(pcm, slots, audio, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
 
     def align_feats(self, slots, feats_list, token_lists, lattice=False, viterbi=True, posteriors=False, band=None, max_passes=1, windows=None):
         """align_pcm from stacked features (lasr_align_feats; with a band lasr_align_band_feats): feats_list as for transcribe_feats."""
-        cat, nf = self._align_feats_input(slots, feats_list)
-        return self._align(self.lib.lasr_align_feats, slots, cat, nf, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
-
-    def _align_feats_input(self, slots, feats_list):
-        """the stacked features of an align_*_feats call concatenated (host, or device when all of them are) and their frame counts"""
-        a, p, n = self._slots(slots)
-        assert len(feats_list) == n
-        F = self.desc.feat
-        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
-            cat = torch.cat([x.reshape(-1, F).float() for x in feats_list]).contiguous()
-            nf = [x.reshape(-1, F).shape[0] for x in feats_list]
-        else:
-            arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
-            cat = np.ascontiguousarray(np.concatenate(arrs))
-            nf = [a_.shape[0] for a_ in arrs]
-        return cat, np.ascontiguousarray(np.array(nf, dtype=np.int32))
+        return self._align_public(False, slots, feats_list, token_lists, lattice, viterbi, posteriors, band, max_passes, windows)
 
     def align_band_post_pcm(self, slots, pcm_list, token_lists, band, max_passes=1, windows=None, lattice=False, viterbi=True):
         """align_pcm(band=...) with the BAND's edge posteriors (lasr_align_band_post_pcm): the dicts of the banded call -- "lo", "width",
@@ -714,74 +673,31 @@ class Engine:
         per label "tok_mean", "tok_var", "tok_peak_frame", "tok_peak" as align_pcm(posteriors=True).  With max_passes > 1 they are
         those of the last pass's windows ("lo").  No path through the windows (loglik -inf): occupancies 0, tok_mean -1, tok_var 0,
         tok_peak_frame -1, tok_peak 0.  At most 2^24 band cells in the call."""
-        cat, ns = self._align_pcm_input(slots, pcm_list)
-        return self._align_band(True, slots, cat, ns, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=True)
+        return self._align(True, slots, pcm_list, token_lists, lattice, viterbi, True, int(band), max_passes, windows)
 
     def align_band_post_feats(self, slots, feats_list, token_lists, band, max_passes=1, windows=None, lattice=False, viterbi=True):
         """align_band_post_pcm from stacked features (lasr_align_band_post_feats): feats_list as for transcribe_feats."""
-        cat, nf = self._align_feats_input(slots, feats_list)
-        return self._align_band(False, slots, cat, nf, token_lists, lattice, viterbi, band, max_passes, windows, posteriors=True)
+        return self._align(False, slots, feats_list, token_lists, lattice, viterbi, True, int(band), max_passes, windows)
 
     def lattice_dp(self, blank, emit, viterbi=True):
         """The lattice dynamic programme alone (lasr_lattice_dp) on caller-supplied lattices: blank / emit = lists of [T_i, U_i + 1]
         float32 arrays (column U_i of emit is not read).  -> per lattice {"loglik", "viterbi", "frames"}."""
-        n = len(blank)
-        assert n == len(emit) and n >= 1
-        bs = [np.asarray(x, dtype=np.float32) for x in blank]
-        es = [np.asarray(x, dtype=np.float32) for x in emit]
-        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
-        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
-        U = np.ascontiguousarray(np.array([x.shape[1] - 1 for x in bs], dtype=np.int32))
-        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
-        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
-        loglik = np.zeros(n, dtype=np.float64)
-        vit = np.zeros(n, dtype=np.float64) if viterbi else None
-        fr = np.zeros(max(int(U.sum()), 1), dtype=np.int32) if viterbi else None
-        self._chk(self.lib.lasr_lattice_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(U), n, _ptr(loglik), _ptr(vit), _ptr(fr)))
-        out, o = [], 0
-        for i in range(n):
-            r = {"loglik": float(loglik[i])}
-            if viterbi:
-                r.update(viterbi=float(vit[i]), frames=fr[o:o + int(U[i])].copy())
-            o += int(U[i])
-            out.append(r)
-        return out
+        _, b, e, T, W = self._lattices(blank, emit)
+        return self._lattice_dp(self.lib.lasr_lattice_dp, (b, e, T, W - 1), viterbi)
 
     def lattice_post(self, blank, emit):
         """Forward-backward alone (lasr_lattice_post) on caller-supplied lattices, blank / emit as for lattice_dp.  -> per lattice
         {"loglik", "loglik_bwd", "occ_blank", "occ_emit" [T, U + 1] float32, "tok_mean", "tok_var", "tok_peak_frame", "tok_peak" [U]}."""
-        n = len(blank)
-        assert n == len(emit) and n >= 1
-        bs = [np.asarray(x, dtype=np.float32) for x in blank]
-        es = [np.asarray(x, dtype=np.float32) for x in emit]
-        assert all(x.ndim == 2 and x.shape == y.shape for x, y in zip(bs, es))
-        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
-        U = np.ascontiguousarray(np.array([x.shape[1] - 1 for x in bs], dtype=np.int32))
-        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
-        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
-        loglik, bwd = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
-        post = self._post_buffers(int(b.size), int(U.sum()))
-        self._chk(self.lib.lasr_lattice_post(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(U), n, _ptr(loglik), _ptr(bwd), *[_ptr(x) for x in post]))
-        out, o, oc = [], 0, 0
-        for i in range(n):
-            t, u = int(T[i]), int(U[i])
-            r = {"loglik": float(loglik[i]), "loglik_bwd": float(bwd[i])}
-            r.update(self._post_slice(post, t, u, oc, o))
-            o += u
-            oc += t * (u + 1)
-            out.append(r)
-        return out
+        _, b, e, T, W = self._lattices(blank, emit)
+        return self._lattice_post(self.lib.lasr_lattice_post, (b, e, T, W - 1), W)
 
     # ------------------------------------------------------------------ n-best rescoring over a prefix tree
     def prefix_tree(self, token_lists):
         """The candidates merged into a prefix tree (lasr_prefix_tree; host only).  -> {"parent", "label", "depth": int32 [N],
         "term": int32 [k], the node of every candidate}: node 0 is the empty prefix, parent[v] < v, depth non-decreasing, the
         children of a node contiguous."""
-        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
-        k = len(toks)
-        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
-        cap = int(nt.sum()) + 1
+        tok, nt = _ragged(token_lists)
+        k, cap = int(nt.size), int(nt.sum()) + 1
         par, lab, dep = (np.zeros(cap, dtype=np.int32) for _ in range(3))
         term = np.zeros(max(k, 1), dtype=np.int32)
         n = C.c_int(0)
@@ -880,56 +796,31 @@ class Engine:
                                                 _ptr(o["inB"]), _ptr(o["node"]), _ptr(o["term"])))
         return o
 
-    def _cat_pcm(self, pcm_list):
-        """-> (all utterances concatenated: one device tensor if every one is, else one host array; int64 sample counts)"""
-        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in pcm_list):
-            cat = torch.cat([x.reshape(-1).float() for x in pcm_list]).contiguous()
-        else:
-            cat = np.ascontiguousarray(np.concatenate([
-                np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1)
-                for x in pcm_list]))
-        return cat, np.ascontiguousarray(np.array([int(np.prod(x.shape)) for x in pcm_list], dtype=np.int64))
-
-    def _cat_feats(self, feats_list):
-        """-> (all [T', feat] blocks concatenated, device or host as _cat_pcm; int32 frame counts)"""
-        F = self.desc.feat
-        if all(isinstance(x, torch.Tensor) and x.is_cuda for x in feats_list):
-            cat = torch.cat([x.reshape(-1, F).float() for x in feats_list]).contiguous()
-            nf = [x.reshape(-1, F).shape[0] for x in feats_list]
-        else:
-            arrs = [np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32).reshape(-1, F) for x in feats_list]
-            cat = np.ascontiguousarray(np.concatenate(arrs))
-            nf = [a_.shape[0] for a_ in arrs]
-        return cat, np.ascontiguousarray(np.array(nf, dtype=np.int32))
-
-    def _score(self, fn, slots_per_utt, cat, lens, cand_lists, viterbi, lattice):
+    def _score(self, pcm, slots_per_utt, audio, cand_lists, viterbi, lattice):
         n = len(slots_per_utt)
+        assert len(audio) == n
+        cat, lens = self._cat_pcm(audio) if pcm else self._cat_feats(audio)
         assert len(cand_lists) == n and all(len(s) == len(c) for s, c in zip(slots_per_utt, cand_lists))
         a, p, K = self._slots([s for grp in slots_per_utt for s in grp])
-        nc = np.ascontiguousarray(np.array([len(c) for c in cand_lists], dtype=np.int32))
-        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for c in cand_lists for t in c]
-        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        nc = np.array([len(c) for c in cand_lists], dtype=np.int32)
+        tok, nt = _ragged([t for c in cand_lists for t in c])
         loglik = np.zeros(max(K, 1), dtype=np.float64)
         vit = np.zeros(max(K, 1), dtype=np.float64) if viterbi else None
-        trees, b, e = None, None, None
+        trees = Ts = Nn = b = e = None
         if lattice:      # the tree is what the library builds from the same candidates; T_i what it derives from the audio
             trees = [self.prefix_tree(c) for c in cand_lists]
-            Ts = self._align_frames(lens, fn is self.lib.lasr_score_pcm)
-            cells = int(sum(int(t) * tr["parent"].size for t, tr in zip(Ts, trees)))
-            b, e = np.zeros(max(cells, 1), dtype=np.float32), np.zeros(max(cells, 1), dtype=np.float32)
+            Ts, Nn = self._align_frames(lens, pcm), [int(tr["parent"].size) for tr in trees]
+            cells = max(sum(t * nn for t, nn in zip(Ts, Nn)), 1)
+            b, e = np.zeros(cells, dtype=np.float32), np.zeros(cells, dtype=np.float32)
+        fn = self.lib.lasr_score_pcm if pcm else self.lib.lasr_score_feats
         self._chk(fn(self.ctx, p, n, _ptr(cat), _ptr(lens), _ptr(nc), _ptr(tok), _ptr(nt), _ptr(loglik), _ptr(vit), _ptr(b), _ptr(e)))
-        out, o, oc = [], 0, 0
-        for i in range(n):
-            k = int(nc[i])
+        out = []
+        for i, k, t, nn, o, oc, _ in self._walk(nc, Ts, Nn):
             r = {"loglik": loglik[o:o + k].copy()}
             if viterbi:
                 r["viterbi"] = vit[o:o + k].copy()
             if lattice:
-                t, nn = int(Ts[i]), int(trees[i]["parent"].size)
-                r.update(tree=trees[i], blank_lp=b[oc:oc + t * nn].reshape(t, nn).copy(), emit_lp=e[oc:oc + t * nn].reshape(t, nn).copy())
-                oc += t * nn
-            o += k
+                r.update(tree=trees[i], blank_lp=_rows(b, oc, t, nn), emit_lp=_rows(e, oc, t, nn))
             out.append(r)
         return out
 
@@ -939,15 +830,11 @@ class Engine:
         utterance i (all distinct); cand_lists[i]: its candidates (non-blank ids).  -> per utterance {"loglik": float64 [k]};
         viterbi=True adds "viterbi" [k]; lattice=True adds "tree" (prefix_tree of the candidates) and "blank_lp" / "emit_lp"
         [T, N] float32 (emit_lp[t, v] = the emission that enters node v).  The slots are left freshly reset."""
-        assert len(pcm_list) == len(slots_per_utt)
-        cat, ns = self._cat_pcm(pcm_list)
-        return self._score(self.lib.lasr_score_pcm, slots_per_utt, cat, ns, cand_lists, viterbi, lattice)
+        return self._score(True, slots_per_utt, pcm_list, cand_lists, viterbi, lattice)
 
     def score_feats(self, slots_per_utt, feats_list, cand_lists, viterbi=False, lattice=False):
         """score_pcm from stacked features (lasr_score_feats): feats_list as for transcribe_feats."""
-        assert len(feats_list) == len(slots_per_utt)
-        cat, nf = self._cat_feats(feats_list)
-        return self._score(self.lib.lasr_score_feats, slots_per_utt, cat, nf, cand_lists, viterbi, lattice)
+        return self._score(False, slots_per_utt, feats_list, cand_lists, viterbi, lattice)
 
     def lm_score(self, slots, token_lists, start=None):
         """log P_LM of every candidate by the attached LM (lasr_lm_score): slots[i] = one open slot per candidate (all distinct, its LM
@@ -956,44 +843,25 @@ class Engine:
         The slots' LM state is left reset (reset(slot, 4)); nothing else changes."""
         a, p, n = self._slots(slots)
         assert len(token_lists) == n
-        toks = [np.asarray(t, dtype=np.int32).reshape(-1) for t in token_lists]
-        nt = np.ascontiguousarray(np.array([t.size for t in toks], dtype=np.int32))
-        tok = np.ascontiguousarray(np.concatenate(toks + [np.zeros(0, np.int32)]))
+        tok, nt = _ragged(token_lists)
         total = np.zeros(max(n, 1), dtype=np.float64)
-        lp = np.zeros(max(int(nt.sum()), 1), dtype=np.float32)
+        lp = np.zeros(max(int(tok.size), 1), dtype=np.float32)
         self._chk(self.lib.lasr_lm_score(self.ctx, p, n, _ptr(tok), _ptr(nt), -1 if start is None else int(start), _ptr(total), _ptr(lp)))
-        out, o = [], 0
-        for i in range(n):
-            out.append({"total": float(total[i]), "logps": lp[o:o + int(nt[i])].copy()})
-            o += int(nt[i])
-        return out
+        return [{"total": float(total[i]), "logps": lp[o:o + u].copy()} for i, u, _, _, o, _, _ in self._walk(nt)]
 
     def lattice_tree_dp(self, blank, emit, parent, viterbi=True):
         """The tree dynamic programme alone (lasr_lattice_tree_dp) on caller-supplied lattices: blank / emit = lists of [T_i, N_i]
         float32 arrays (emit[:, 0] is not read), parent = lists of N_i node ids (-1 at node 0, parent[v] < v, depth
         non-decreasing).  -> per lattice {"loglik": float64 [N_i], "viterbi": float64 [N_i]}: log P(prefix_v | x) per node."""
-        n = len(blank)
-        assert n == len(emit) == len(parent) and n >= 1
-        bs = [np.asarray(x, dtype=np.float32) for x in blank]
-        es = [np.asarray(x, dtype=np.float32) for x in emit]
-        ps = [np.asarray(x, dtype=np.int32).reshape(-1) for x in parent]
-        assert all(x.ndim == 2 and x.shape == y.shape and x.shape[1] == q.size for x, y, q in zip(bs, es, ps))
-        T = np.ascontiguousarray(np.array([x.shape[0] for x in bs], dtype=np.int32))
-        Nn = np.ascontiguousarray(np.array([x.shape[1] for x in bs], dtype=np.int32))
-        b = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in bs]))
-        e = np.ascontiguousarray(np.concatenate([x.reshape(-1) for x in es]))
-        par = np.ascontiguousarray(np.concatenate(ps))
+        n, b, e, T, Nn = self._lattices(blank, emit)
+        assert n == len(parent)
+        par, sizes = _ragged(parent)
+        assert np.array_equal(sizes, Nn)
         loglik = np.zeros(int(Nn.sum()), dtype=np.float64)
         vit = np.zeros(int(Nn.sum()), dtype=np.float64) if viterbi else None
         self._chk(self.lib.lasr_lattice_tree_dp(self.ctx, _ptr(b), _ptr(e), _ptr(T), _ptr(Nn), _ptr(par), n, _ptr(loglik), _ptr(vit)))
-        out, o = [], 0
-        for i in range(n):
-            r = {"loglik": loglik[o:o + int(Nn[i])].copy()}
-            if viterbi:
-                r["viterbi"] = vit[o:o + int(Nn[i])].copy()
-            o += int(Nn[i])
-            out.append(r)
-        return out
+        return [{"loglik": loglik[o:o + k].copy(), **({"viterbi": vit[o:o + k].copy()} if viterbi else {})}
+                for _, k, _, _, o, _, _ in self._walk(Nn)]
 
     # ------------------------------------------------------------------ op-level (tests, microbench)
     def logmel(self, pcm):
