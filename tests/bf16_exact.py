@@ -132,10 +132,11 @@ class StandIn:
     """OracleTransducer.encoder / .predictor / .joint_logp restated on the oracle's own functions and weights so that every stage
     can be read -- the float32 evaluation of the yardstick, and with a mutation switched on the subtly wrong kernel of the
     sensitivity tests: q = the activation rounding, raw_h_t = time step that is fed an unrounded h, raw_act = the vocabulary GEMM is
-    fed the unrounded joint activation (weight mutations are made on a copy of the oracle: mutated())."""
+    fed the unrounded joint activation, stale_c_t = time step whose LSTM cells read the learned initial cell state instead of the
+    previous step's (weight mutations are made on a copy of the oracle: mutated())."""
 
-    def __init__(self, o, q=None, raw_h_t=None, raw_act=False):
-        self.o, self.q, self.raw_h_t, self.raw_act = o, (q or o.q), raw_h_t, raw_act
+    def __init__(self, o, q=None, raw_h_t=None, raw_act=False, stale_c_t=None):
+        self.o, self.q, self.raw_h_t, self.raw_act, self.stale_c_t = o, (q or o.q), raw_h_t, raw_act, stale_c_t
 
     def encoder(self, x):
         o, q, s = self.o, self.q, {}
@@ -144,9 +145,9 @@ class StandIn:
         x = s["x0"] = q(s["x0.pre"])
         for l, L in enumerate(o.enc):
             h, c = q(np.repeat(L["hs"][0, 0], B, 0).copy()), np.repeat(L["hs"][1, 0], B, 0).copy()
-            ys = np.empty((B, T, o.H), F32)
+            ys, c_init = np.empty((B, T, o.H), F32), c
             for t in range(T):
-                h, c = O.lstm_step(x[:, t], h, c, L["rnn"])
+                h, c = O.lstm_step(x[:, t], h, c_init if self.stale_c_t == t else c, L["rnn"])
                 ys[:, t] = h
                 s[f"enc{l}.t{t}.c"], s[f"enc{l}.t{t}.h.pre"] = c, h
                 h = s[f"enc{l}.t{t}.h"] = q(h)
@@ -161,6 +162,7 @@ class StandIn:
         o, q, s = self.o, self.q, {}
         B, U = toks.shape
         st = [(q(np.repeat(L["hs"][0, 0], B, 0).copy()), np.repeat(L["hs"][1, 0], B, 0).copy() if o.pred_lstm else None) for L in o.pred]
+        c_init = [c for _, c in st]
         for u in range(U):
             x = o.embed[toks[:, u]]
             if o.ffn_w is not None:
@@ -168,7 +170,7 @@ class StandIn:
             for l, L in enumerate(o.pred):
                 h0, c0 = st[l]
                 if o.pred_lstm:
-                    h, c = O.lstm_step(x, h0, c0, L["rnn"])
+                    h, c = O.lstm_step(x, h0, c_init[l] if self.stale_c_t == u else c0, L["rnn"])
                     s[f"pred{l}.u{u}.c"] = c
                 else:
                     h, c = O.nbrc_step(x, h0, L["rnn"]), None
