@@ -32,6 +32,22 @@ int lasr_debug_timing(lasr_ctx* c, unsigned long long* out);
  *       10: (LASR_DBG_ENCLOG + LASR_DBG_PENDLOG=1) the pending log-mel frames as they were behind logged step `index`
  *        9: integers as floats [8][M]: device ring position, host mirror, chunks pushed, frames pending, frames of the
  *           last step, frame cursor, last token, emitted flag
+ * The attached LM (LASR_ESTATE without one), rows R = M * beam (streams, or hypothesis slots with a beam), at the parity the
+ * context currently holds:
+ *       11 / 12: LM h / c of layer `index`                                     [R][lm hidden]
+ *       13: the output layer's logits of the last LM step                      [R][vocab]
+ *       14: the standardised vector the fuser reads (mean subtracted twice, unbiased std + 1e-5, entry 0 = min_val)  [R][vocab]
+ *       15: the rows' "has a distribution" flags as floats                     [1][R]
+ *       16: the layer-0 input table                                            [vocab][4 * lm hidden]
+ *       17: int8-served form only (else LASR_ESTATE): the quantised image of h of layer `index`, integers as floats, the
+ *           padding columns included                                           [M][lm hidden rounded up to 32]
+ *       18: int8-served form only: the scales of those images                  [lm layers][M]
+ *     What they hold is defined by two properties of the engine, which the tests of tests/test_gpu_lm_exact.py rely on (a change
+ *     of either has to keep them or move those tests): (a) lasr_lm_score steps the LM teacher-forced on the listed rows and its
+ *     closing reset zeroes h, c, the quantised images and flag 15 of those rows (scales 18: 0.1) but leaves 13 and 14 as the last
+ *     pass wrote them -- after a call in which every listed candidate has the same number of passes, 13 holds every listed
+ *     row's logits of the last pass and 14 what k_lm_post made of them; (b) 11, 12, 17 and 18 survive a decode and equal the LM
+ *     run from zero state over the tokens the row has emitted since its last LM reset (13 / 14: the step on the last of them).
  * M = max_streams rounded up to 64.  LASR_EFULL if cap is too small (*rows / *cols are set). */
 int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, int* rows, int* cols);
 

@@ -3092,7 +3092,8 @@ int lasr_trace_read(lasr_ctx* c, double* us, int* tags, int cap, int* n) {
 // parity); 3 pe (joint encoder half, synchronous buffer) of frame `index`; 4 pp; 5 pred_h of layer `index` (current parity,
 // decoder rows); 6 PCM ring [M][ring_chunks * chunk]; 7 pending log-mel frames [M][n_buffer * n_stack * n_mels];
 // 8 last encoder layer's output of frame `index`; 9 integers as floats [8][M]: ring_pos, host ring mirror, n_chunks,
-// n_pend, T_row_fix, t_idx, token, emit.  *rows / *cols (optional) describe the matrix; cap = floats `out` holds.
+// n_pend, T_row_fix, t_idx, token, emit; 11..18 the attached LM's state (lasr_debug.h).  *rows / *cols (optional) describe the
+// matrix; cap = floats `out` holds.
 int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, int* rows, int* cols) {
     if (!c || !out) return LASR_EINVAL;
     RC(drain(c, false));
@@ -3100,8 +3101,17 @@ int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, in
     const int M = c->M, H = d.hidden, F = d.feat, J = d.joint;
     int R = M, K = 0;
     const int mt_total = c->Tcap * c->MT;
-    enum { FRAG, ROWMAJ_ELEM, ROWMAJ_F32, UNITMAJ, INTS } kind = ROWMAJ_F32;
+    enum { FRAG, ROWMAJ_ELEM, ROWMAJ_F32, UNITMAJ, INTS, INT_ROW, LM_SXH } kind = ROWMAJ_F32;
     const void* src = nullptr; int frag_mt_total = 0, frag_mt_off = 0;
+    int elem_bf = c->bf, unit_ld = M;      // element type of a ROWMAJ_ELEM source; row count of a UNITMAJ source
+    // the LM's rows (11..18): streams, or hypothesis slots with a beam, at the parity the context holds (see lasr_debug.h)
+    const lasr_ctx::LM& lm = c->lm;
+    const bool lm_beam = c->W > 1;
+    if (what >= 11 && what <= 18) {
+        if (!lm.on) return fail(c, LASR_ESTATE, "no LM attached");
+        if ((what == 17 || what == 18) && !lm.q8) return fail(c, LASR_ESTATE, "the quantised image of h exists in the int8-served form only");
+        if ((what == 11 || what == 12 || what == 17) && (index < 0 || index >= lm.L)) return fail(c, LASR_EINVAL, "layer out of range");
+    }
     switch (what) {
         case 0: if (index < 0 || index >= c->Tcap) return fail(c, LASR_EINVAL, "frame out of range");
                 kind = FRAG; src = c->x0; K = F; frag_mt_total = mt_total; frag_mt_off = index * c->MT; break;
@@ -3121,6 +3131,16 @@ int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, in
         case 9: kind = INTS; R = 8; K = M; break;
         case 10: if (!c->pendlog || index < 0 || index >= c->enclog_cap) return fail(c, LASR_EINVAL, "no pending-frame log (LASR_DBG_ENCLOG + LASR_DBG_PENDLOG) or step out of range");
                 kind = ROWMAJ_F32; K = d.n_buffer * d.n_stack * d.n_mels; src = c->pendlog + (size_t)index * M * K; break;
+        case 11: R = c->Md; K = lm.H; src = lm.h[lm.q8 ? 0 : lm.par][index];
+                 if (lm.q8) kind = ROWMAJ_F32; else kind = ROWMAJ_ELEM;
+                 break;
+        case 12: kind = UNITMAJ; R = c->Md; K = lm.H; unit_ld = R; src = lm.cst[par_rd(lm_beam, lm.par)][index]; break;
+        case 13: kind = ROWMAJ_F32; R = c->Md; K = d.vocab; src = lm.raw; break;
+        case 14: kind = ROWMAJ_F32; R = c->Md; K = d.vocab; src = lm.lmz[par_rd(lm_beam, lm.par)]; break;
+        case 15: kind = INT_ROW; R = 1; K = c->Md; src = lm.valid[par_rd(lm_beam, lm.par)]; break;
+        case 16: kind = ROWMAJ_F32; R = d.vocab; K = 4 * lm.H; src = lm.cells[0].tab; break;
+        case 17: kind = ROWMAJ_ELEM; elem_bf = 1; K = lm.Kp_h; src = lm.qh[index]; break;
+        case 18: kind = LM_SXH; R = lm.L; K = M; break;
         default: return fail(c, LASR_EINVAL, "unknown debug read %d", what);
     }
     if (rows) *rows = R;
@@ -3141,14 +3161,24 @@ int lasr_debug_read(lasr_ctx* c, int what, int index, float* out, size_t cap, in
         HIPCHK(c, hipMemcpy(out, src, sizeof(float) * (size_t)R * K, hipMemcpyDeviceToHost));
         return LASR_OK;
     }
+    if (kind == INT_ROW) {
+        std::vector<int> tmp(K);
+        HIPCHK(c, hipMemcpy(tmp.data(), src, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost));
+        for (int r = 0; r < K; ++r) out[r] = (float)tmp[r];
+        return LASR_OK;
+    }
+    if (kind == LM_SXH) {
+        for (int l = 0; l < R; ++l) HIPCHK(c, hipMemcpy(out + (size_t)l * K, lm.sxh[l], sizeof(float) * (size_t)K, hipMemcpyDeviceToHost));
+        return LASR_OK;
+    }
     float* tmp = nullptr;
     RC(dalloc(c, &tmp, (size_t)R * K));
     if (kind == FRAG)
         hipLaunchKernelGGL(k_from_frag, dim3(grid1((size_t)R * K)), dim3(256), 0, c->stream, src, frag_mt_total, frag_mt_off, tmp, K, R, K, c->bf);
     else if (kind == ROWMAJ_ELEM)
-        hipLaunchKernelGGL(k_from_elem, dim3(grid1((size_t)R * K)), dim3(256), 0, c->stream, src, tmp, (size_t)R * K, c->bf);
+        hipLaunchKernelGGL(k_from_elem, dim3(grid1((size_t)R * K)), dim3(256), 0, c->stream, src, tmp, (size_t)R * K, elem_bf);
     else
-        hipLaunchKernelGGL(k_c_to_rows, dim3(grid1((size_t)R * K)), dim3(256), 0, c->stream, (const float*)src, M, tmp, R, K);
+        hipLaunchKernelGGL(k_c_to_rows, dim3(grid1((size_t)R * K)), dim3(256), 0, c->stream, (const float*)src, unit_ld, tmp, R, K);
     hipError_t e = hipMemcpy(out, tmp, sizeof(float) * (size_t)R * K, hipMemcpyDeviceToHost);
     dfree(c, tmp);
     if (e != hipSuccess) return fail(c, LASR_EHIP, "debug read copy failed: %s", hipGetErrorString(e));

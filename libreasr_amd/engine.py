@@ -936,7 +936,8 @@ class Engine:
     def sync(self):
         self._chk(self.lib.lasr_sync(self.ctx))
 
-    DEBUG_READS = dict(x0=0, enc_h=1, enc_c=2, pe=3, pp=4, pred_h=5, ring=6, pend=7, enc_out=8, ints=9, pendlog=10)
+    DEBUG_READS = dict(x0=0, enc_h=1, enc_c=2, pe=3, pp=4, pred_h=5, ring=6, pend=7, enc_out=8, ints=9, pendlog=10,
+                       lm_h=11, lm_c=12, lm_raw=13, lmz=14, lm_valid=15, lm_tab=16, lm_qh=17, lm_sxh=18)
 
     def debug_read(self, what, index=0):
         """Resident state as a [rows, cols] float32 array (lasr_debug_read; tests and the soak tool)."""

@@ -238,7 +238,11 @@ def static_entry(k0, k1, nw):
 def launches(launcher, cfg):
     """[(k0, k1)] of the GEMM launches of one pass: "enc_cell" one per layer (x phase K = feat or hidden, h phase K = hidden);
     "pred_cell" one per layer (layer 0's x phase is the token table: absent); "joint_half" pp and pe (one phase, K = hidden);
-    "logits" (one phase, K = joint)"""
+    "logits" (one phase, K = joint); of an LM step (cfg: an LM config; launch_lm_t): "lm_cell" one per layer (layer 0's x phase is
+    the token table: absent), "lm_out" the output layer (one phase, K = hidden)"""
+    if launcher in ("lm_cell", "lm_out"):
+        H = cfg["hidden"] // KCH
+        return [(None if l == 0 else H, H) for l in range(cfg["layers"])] if launcher == "lm_cell" else [(H, None)]
     F, H, J = cfg["feat"] // KCH, cfg["hidden"] // KCH, cfg["joint"] // KCH
     if launcher == "enc_cell":
         return [(F if l == 0 else H, H) for l in range(cfg["enc_layers"])]
@@ -248,8 +252,9 @@ def launches(launcher, cfg):
 
 
 def schedule(launcher, name, nw):
-    """the static entries (None: dynamic) of the launches of `launcher` for model `name` on nw waves"""
-    return [static_entry(k0, k1, nw) for k0, k1 in launches(launcher, model_cfg(name))]
+    """the static entries (None: dynamic) of the launches of `launcher` for model `name` (a config dict is taken as it is: the LM
+    kinds) on nw waves"""
+    return [static_entry(k0, k1, nw) for k0, k1 in launches(launcher, name if isinstance(name, dict) else model_cfg(name))]
 
 
 # ----------------------------------------------------------------------------- the cases of tests/test_gpu_f32_exact.py
